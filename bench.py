@@ -7,6 +7,11 @@ GPU over RCCL; this script reads RANK/LOCAL_RANK/WORLD_SIZE from the env.
 W untimed warmup steps, then exactly K timed steps bracketed by a barrier +
 torch.cuda.synchronize on both sides; elapsed time is MAX over ranks; rank 0
 prints one JSON line with the whole-node aggregate tokens/sec.
+A plain run does only that: plan, build, warm up, time, report.
+`--dump-outputs DIR` also writes the last timed step's loss and a seeded
+sample of the updated parameters to DIR/*.npy; seeds are fixed, so the same
+arguments give the same inputs and two builds compare output for output.
+`--full` is where any further measurement or check belongs (none today).
 
 Auto-parallel (default): the model's IR goes through the AutoParallel
 planner (exploration mode) and the PLANNED GRAPH IS WHAT EXECUTES — the
@@ -59,6 +64,34 @@ def plan_parallelism(cfg, world: int, global_batch: int, seq: int,
     return plan.dp, plan.tp, plan.pp, plan.micro_batches, search, plan
 
 
+DUMP_SAMPLE_PER_TENSOR = 8192
+
+
+def dump_outputs(out_dir: str, loss, module: torch.nn.Module):
+    """Writes what the last timed step handed back: its loss (the value
+    train_step returns) and the parameters it updated. Parameters go out as
+    one float32 vector holding, per tensor in name order, a fixed seeded
+    sample of DUMP_SAMPLE_PER_TENSOR elements (the whole tensor if smaller),
+    a few MB for any model here."""
+    import os
+
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"),
+            np.asarray([float(loss)], dtype=np.float64))
+    gen = torch.Generator().manual_seed(97531)
+    parts = []
+    for _, p in sorted(module.named_parameters(), key=lambda kv: kv[0]):
+        flat = p.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE_PER_TENSOR:
+            idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE_PER_TENSOR,),
+                                generator=gen)
+            flat = flat[idx.to(flat.device)]
+        parts.append(flat.float().cpu())
+    np.save(os.path.join(out_dir, "params_sample.npy"),
+            torch.cat(parts).numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -72,7 +105,16 @@ def main():
                     help="auto | dp | tp<N> | pp<N>")
     ap.add_argument("--device", type=str, default=None,
                     help="override device (cpu for plumbing tests)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed "
+                         "step computed to DIR/<name>.npy (rank 0's view)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements and checks that the "
+                         "headline figure does not need (none today: the "
+                         "plain run is already only plan, warm up, time)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank, world, local_rank = init_distributed()
     if args.device is not None:
@@ -287,6 +329,10 @@ def main():
     tokens_per_step = rows_per_step * seq
     ms_per_step = elapsed / args.steps * 1000.0
     tokens_per_sec = tokens_per_step * args.steps / elapsed
+
+    if rank == 0 and args.dump_outputs:
+        # flat-mesh paths hold the parameters in `model`, pipelines in `mod`
+        dump_outputs(args.dump_outputs, loss, model if pp == 1 else mod)
 
     if rank == 0:
         print(json.dumps({

@@ -38,13 +38,13 @@ def test_wide_resnet_gpu_trains():
     assert losses[-1] < losses[0] * 1.05, losses
 
 
-def test_rpc_service_gpu_step():
+def test_rpc_service_gpu_step(tmp_path):
     """Server-side IR interpreter executes on the GPU through the kernels."""
     from tepdist_amd.ir import gpt2_ir
     from tepdist_amd.models.configs import GPT2_CONFIGS
     from tepdist_amd.rpc.service import TepdistService
     cfg = GPT2_CONFIGS["gpt2-test"]
-    svc = TepdistService(ckpt_dir="/tmp/tepdist_gpu_ckpt")
+    svc = TepdistService(ckpt_dir=str(tmp_path / "ckpt"))
     assert svc.device.startswith("cuda")
     g = gpt2_ir(cfg, batch=4, seq=16)
     r = svc.build_execution_plan({"graph": g.to_json(), "num_devices": 1})
