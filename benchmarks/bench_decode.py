@@ -1,6 +1,8 @@
 """Serving-path benchmark: prefill + decode throughput of the KV-cache
 generation engine (inference/engine.py) on one GPU. Prints one JSON line
-per config: prefill tokens/s and steady-state decode tokens/s."""
+per config: prefill tokens/s and steady-state decode tokens/s, with the
+decode-attention mode in use (TEPDIST_DECODE_ATTN=fused|composed|auto;
+compare modes by alternating runs in one GPU visit)."""
 import json
 import os
 import sys
@@ -39,6 +41,10 @@ def main(name="gpt2-345m", batch=32, prompt=512, new=128):
     print(json.dumps({
         "bench": "decode", "config": name, "batch": batch,
         "prompt": prompt, "new_tokens": n_new, "dtype": "bf16",
+        "decode_attn": g.decode_attn,
+        "decode_attn_fused": g._fused_decode(
+            out.new_empty(0, dtype=torch.bfloat16),
+            cfg.n_embd // cfg.n_head),
         "prefill_tokens_per_s": round(batch * prompt / pre, 1),
         "decode_tokens_per_s": round(dec, 1),
         "total_s": round(dt, 3)}), flush=True)

@@ -2,10 +2,15 @@
 reference's training-only scope).
 
 Prefill runs the flash kernels over the whole prompt while recording K/V;
-decode steps run one token at a time against the cache with composed
-batched matmuls (at q_len = 1 the GEMV-shaped attention is bandwidth
-bound — the cache layout [B, H, S_max, D] keeps the K/V reads
-contiguous). The engine reads the model's parameters directly (tp = 1
+decode steps run one token at a time against the cache (at q_len = 1 the
+GEMV-shaped attention is bandwidth bound — the cache layout
+[B, H, S_max, D] keeps the K/V reads contiguous). decode_attn selects how:
+"fused" = ops.decode_attention, one kernel per layer that appends the new
+K/V row and attends over the valid rows only; "composed" = batched
+matmuls + softmax over the cache; "auto" (default, or
+TEPDIST_DECODE_ATTN) = fused for bf16 with head dim 64/128 on the GPU
+(measured +51% decode tokens/s, docs/KERNELS.md), composed otherwise and
+on CPU. The engine reads the model's parameters directly (tp = 1
 layout of models/gpt2.py), so no changes to the training forward."""
 
 from __future__ import annotations
@@ -20,11 +25,31 @@ from tepdist_amd import ops
 
 
 class Generator:
-    def __init__(self, model, max_seq: Optional[int] = None):
+    def __init__(self, model, max_seq: Optional[int] = None,
+                 decode_attn: Optional[str] = None):
         assert model.env.tp_size == 1, "generation engine: tp=1 layout"
         self.m = model
         self.cfg = model.cfg
         self.max_seq = max_seq or self.cfg.n_ctx
+        if decode_attn is None:
+            decode_attn = os.environ.get("TEPDIST_DECODE_ATTN", "auto")
+        if decode_attn not in ("fused", "composed", "auto"):
+            raise ValueError(
+                f"decode_attn must be 'fused', 'composed' or 'auto', "
+                f"got {decode_attn!r}")
+        self.decode_attn = decode_attn
+
+    def _fused_decode(self, x, D) -> bool:
+        """Whether single-token steps on tensors like x run the fused
+        ops.decode_attention. On CUDA the kernel covers bf16 with head dim
+        64/128; anything else stays composed (same policy as
+        hip.attention_fwd). On CPU only an explicit "fused" selects the
+        reference op, so "auto" leaves the CPU engine as it was."""
+        if self.decode_attn == "composed":
+            return False
+        if x.is_cuda:
+            return x.dtype == torch.bfloat16 and D in (64, 128)
+        return self.decode_attn == "fused"
 
     # -- one transformer stack pass over new tokens x [B, T, d], with
     # caches kc/vc [L][B, H, S_max, D] filled up to `pos` -----------------
@@ -35,33 +60,44 @@ class Generator:
         H = cfg.n_head
         D = d // H
         scale = 1.0 / math.sqrt(D)
+        fused = T == 1 and self._fused_decode(x, D)
+        if fused:
+            pos_t = torch.full((1,), pos, device=x.device, dtype=torch.long)
         for li, blk in enumerate(self.m.blocks):
             h = ops.layernorm(x, blk.ln1_g, blk.ln1_b, cfg.ln_eps)
             qkv = ops.linear(h, blk.w_qkv, blk.b_qkv)      # [B,T,3d]
-            q, k, v = qkv.split(d, dim=-1)
-
-            def heads(t):
-                return t.reshape(B, T, H, D).transpose(1, 2)  # [B,H,T,D]
-            qh, kh, vh = heads(q), heads(k), heads(v)
-            kc[li][:, :, pos:pos + T] = kh
-            vc[li][:, :, pos:pos + T] = vh
-            if T > 1 and pos == 0:
-                a = ops.attention(qh.contiguous(), kh.contiguous(),
-                                  vh.contiguous(), causal=True)
+            if fused:
+                # one kernel: cache append at pos + attention over 0..pos,
+                # reading q/k/v as views of the packed projection
+                q3 = qkv.view(B, 3, H, D)
+                a = ops.decode_attention(q3[:, 0], kc[li], vc[li], pos_t,
+                                         k_new=q3[:, 1],
+                                         v_new=q3[:, 2]).reshape(B, 1, d)
             else:
-                # decode: q over the whole cache (composed, GEMV-shaped)
-                kall = kc[li][:, :, :pos + T]
-                vall = vc[li][:, :, :pos + T]
-                scores = ops.matmul(qh.contiguous(),
-                                    kall.transpose(-1, -2)) * scale
-                if T > 1:  # chunked prefill continuation: causal inside
-                    qpos = torch.arange(pos, pos + T, device=x.device)
-                    kpos = torch.arange(pos + T, device=x.device)
-                    mask = kpos[None, :] > qpos[:, None]
-                    scores = scores.masked_fill(mask, float("-inf"))
-                p = torch.softmax(scores.float(), dim=-1).to(vall.dtype)
-                a = ops.matmul(p, vall.contiguous())
-            a = a.transpose(1, 2).reshape(B, T, d)
+                q, k, v = qkv.split(d, dim=-1)
+
+                def heads(t):
+                    return t.reshape(B, T, H, D).transpose(1, 2)  # [B,H,T,D]
+                qh, kh, vh = heads(q), heads(k), heads(v)
+                kc[li][:, :, pos:pos + T] = kh
+                vc[li][:, :, pos:pos + T] = vh
+                if T > 1 and pos == 0:
+                    a = ops.attention(qh.contiguous(), kh.contiguous(),
+                                      vh.contiguous(), causal=True)
+                else:
+                    # decode: q over the whole cache (composed, GEMV-shaped)
+                    kall = kc[li][:, :, :pos + T]
+                    vall = vc[li][:, :, :pos + T]
+                    scores = ops.matmul(qh.contiguous(),
+                                        kall.transpose(-1, -2)) * scale
+                    if T > 1:  # chunked prefill continuation: causal inside
+                        qpos = torch.arange(pos, pos + T, device=x.device)
+                        kpos = torch.arange(pos + T, device=x.device)
+                        mask = kpos[None, :] > qpos[:, None]
+                        scores = scores.masked_fill(mask, float("-inf"))
+                    p = torch.softmax(scores.float(), dim=-1).to(vall.dtype)
+                    a = ops.matmul(p, vall.contiguous())
+                a = a.transpose(1, 2).reshape(B, T, d)
             x = x + ops.linear(a, blk.w_proj, blk.b_proj)
             h = ops.layernorm(x, blk.ln2_g, blk.ln2_b, cfg.ln_eps)
             h = ops.linear(h, blk.w_fc, blk.b_fc, act="gelu")
@@ -90,22 +126,32 @@ class Generator:
         scale = 1.0 / math.sqrt(D)
         x = ops.embedding(tok.reshape(-1), self.m.wte).reshape(B, 1, d) \
             + ops.embedding(cur_t, self.m.wpe)
-        mask = (kpos > cur_t)                       # [S_max] device bool
+        fused = self._fused_decode(x, D)
+        if not fused:
+            mask = (kpos > cur_t)                   # [S_max] device bool
         for li, blk in enumerate(self.m.blocks):
             h = ops.layernorm(x, blk.ln1_g, blk.ln1_b, cfg.ln_eps)
             qkv = ops.linear(h, blk.w_qkv, blk.b_qkv)
-            q, k, v = qkv.split(d, dim=-1)
-            qh = q.reshape(B, 1, H, D).transpose(1, 2)
-            kc[li].index_copy_(2, cur_t,
-                               k.reshape(B, 1, H, D).transpose(1, 2))
-            vc[li].index_copy_(2, cur_t,
-                               v.reshape(B, 1, H, D).transpose(1, 2))
-            scores = ops.matmul(qh.contiguous(),
-                                kc[li].transpose(-1, -2)) * scale
-            scores = scores.masked_fill(mask, float("-inf"))
-            p = torch.softmax(scores.float(), dim=-1).to(x.dtype)
-            a = ops.matmul(p, vc[li])
-            a = a.transpose(1, 2).reshape(B, 1, d)
+            if fused:
+                # the kernel reads cur_t on the device: appends k/v at
+                # cur_t and attends rows 0..cur_t only (no S_max sweep)
+                q3 = qkv.view(B, 3, H, D)
+                a = ops.decode_attention(q3[:, 0], kc[li], vc[li], cur_t,
+                                         k_new=q3[:, 1],
+                                         v_new=q3[:, 2]).reshape(B, 1, d)
+            else:
+                q, k, v = qkv.split(d, dim=-1)
+                qh = q.reshape(B, 1, H, D).transpose(1, 2)
+                kc[li].index_copy_(2, cur_t,
+                                   k.reshape(B, 1, H, D).transpose(1, 2))
+                vc[li].index_copy_(2, cur_t,
+                                   v.reshape(B, 1, H, D).transpose(1, 2))
+                scores = ops.matmul(qh.contiguous(),
+                                    kc[li].transpose(-1, -2)) * scale
+                scores = scores.masked_fill(mask, float("-inf"))
+                p = torch.softmax(scores.float(), dim=-1).to(x.dtype)
+                a = ops.matmul(p, vc[li])
+                a = a.transpose(1, 2).reshape(B, 1, d)
             x = x + ops.linear(a, blk.w_proj, blk.b_proj)
             h = ops.layernorm(x, blk.ln2_g, blk.ln2_b, cfg.ln_eps)
             h = ops.linear(h, blk.w_fc, blk.b_fc, act="gelu")

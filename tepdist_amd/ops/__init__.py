@@ -8,6 +8,7 @@ from tepdist_amd.ops.interface import (  # noqa: F401
     softmax,
     attention,
     attention_qkv,
+    decode_attention,
     embedding,
     cross_entropy,
     dropout,

@@ -26,6 +26,7 @@ SOURCES = [
     "gemm.hip",
     "gemm256.hip",
     "attention.hip",
+    "decode_attention.hip",
     "transpose.hip",
     "layernorm.hip",
     "softmax.hip",

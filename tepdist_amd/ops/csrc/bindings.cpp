@@ -142,8 +142,26 @@ PYBIND11_MODULE(_tepdist_hip, m) {
     check_launch();
   });
 
+  m.def("decode_attention", [](uintptr_t q, uintptr_t k_new, uintptr_t v_new,
+                               uintptr_t k_cache, uintptr_t v_cache,
+                               uintptr_t pos, int pos_stride, uintptr_t out,
+                               uintptr_t ws, int B, int H, int S_max, int D,
+                               float scale, int splits, int64_t q_bs,
+                               int64_t q_hs, int64_t n_bs, int64_t n_hs,
+                               int64_t c_bs, int64_t c_hs, int64_t c_rs,
+                               uintptr_t stream) {
+    decode_attention_bf16(
+        reinterpret_cast<void*>(q), reinterpret_cast<void*>(k_new),
+        reinterpret_cast<void*>(v_new), reinterpret_cast<void*>(k_cache),
+        reinterpret_cast<void*>(v_cache),
+        reinterpret_cast<const int64_t*>(pos), pos_stride,
+        reinterpret_cast<void*>(out), reinterpret_cast<float*>(ws), B, H,
+        S_max, D, scale, splits, q_bs, q_hs, n_bs, n_hs, c_bs, c_hs, c_rs,
+        S(stream));
+    check_launch();
+  });
 
-  m.def("embedding_fwd", [](uintptr_t ids, uintptr_t table, uintptr_t out,
+  m.def("embedding_fwd",[](uintptr_t ids, uintptr_t table, uintptr_t out,
                             int64_t n_ids, int dim, uintptr_t stream) {
     embedding_fwd_bf16(reinterpret_cast<const int64_t*>(ids),
                        reinterpret_cast<void*>(table),

@@ -89,6 +89,25 @@ void attention_bwd_bf16(const void* q, const void* k, const void* v,
                         int64_t o_bs, int64_t o_hs, int64_t o_rs,
                         hipStream_t stream);
 
+// --- Decode attention (single query over a KV cache) ----------------------
+// q/k_new/v_new: [B,H,D] bf16, D contiguous, (bs, hs) element strides
+// (q_* for q, n_* shared by k_new/v_new; both may be null). k/v_cache:
+// [B,H,S_max,D] bf16 sharing (c_bs, c_hs, c_rs). pos: device int64, read
+// at pos[b * pos_stride] (pos_stride 0 or 1) and clamped into
+// [0, S_max-1] in the kernel. Without new rows the query attends cache
+// rows 0..p; with them it attends rows 0..p-1 plus the new row, which is
+// also stored into cache[b,:,p,:] (equal to write-then-attend; cache row p
+// is never read by that launch). out: [B,H,D] bf16 contiguous. ws: fp32
+// [B*H*splits*(D+2)], only read when splits > 1. D in {64,128},
+// splits in [1,32]; anything else throws.
+void decode_attention_bf16(const void* q, const void* k_new,
+                           const void* v_new, void* k_cache, void* v_cache,
+                           const int64_t* pos, int pos_stride, void* out,
+                           float* ws, int B, int H, int S_max, int D,
+                           float scale, int splits, int64_t q_bs,
+                           int64_t q_hs, int64_t n_bs, int64_t n_hs,
+                           int64_t c_bs, int64_t c_hs, int64_t c_rs,
+                           hipStream_t stream);
 
 // --- Embedding -------------------------------------------------------------
 void embedding_fwd_bf16(const int64_t* ids, const void* table, void* out,

@@ -270,6 +270,26 @@ def attention_qkv(qkv, heads: int, causal: bool = True):
     return AttentionQKVFn.apply(qkv, heads, causal)
 
 
+def decode_attention(q, k_cache, v_cache, positions, k_new=None, v_new=None,
+                     scale: Optional[float] = None,
+                     splits: Optional[int] = None):
+    """Single-query attention over a KV cache (inference only, no
+    autograd). q/k_new/v_new [B, H, D], caches [B, H, S_max, D],
+    positions int64 [1] or [B] on the tensors' device. With (k_new, v_new)
+    the new row is written in place into cache[b, :, positions[b]] and
+    attended to; otherwise cache rows 0..positions[b] are attended.
+    `splits` (GPU only) pins the KV split count; None = host heuristic."""
+    for t in (q, k_cache, v_cache, k_new, v_new):
+        assert t is None or not t.requires_grad, \
+            "decode_attention has no backward"
+    be = _backend(q)
+    if be is ref:
+        return ref.decode_attention(q, k_cache, v_cache, positions, k_new,
+                                    v_new, scale)
+    return be.decode_attention(q, k_cache, v_cache, positions, k_new, v_new,
+                               scale, splits)
+
+
 # --------------------------------------------------------------------------
 
 

@@ -192,6 +192,37 @@ def attention_qkv_bwd(dout: torch.Tensor, qkv: torch.Tensor, heads: int,
     return torch.cat([back(dq), back(dk), back(dv)], dim=-1)
 
 
+def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
+                     v_cache: torch.Tensor, positions: torch.Tensor,
+                     k_new: Optional[torch.Tensor] = None,
+                     v_new: Optional[torch.Tensor] = None,
+                     scale: Optional[float] = None) -> torch.Tensor:
+    """Single-query attention over a KV cache. q/k_new/v_new: [B, H, D];
+    k_cache/v_cache: [B, H, S_max, D]; positions: int64 [1] or [B], clamped
+    into [0, S_max-1]. With (k_new, v_new) the new row is first written
+    IN PLACE into cache[b, :, p[b]]; batch row b then attends cache rows
+    0..p[b] inclusive. Rows above p[b] have no influence whatever they hold
+    (NaN included). fp32 math, returns [B, H, D] in q.dtype."""
+    assert (k_new is None) == (v_new is None)
+    B, H, D = q.shape
+    S_max = k_cache.shape[2]
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    pos = positions.reshape(-1).long().clamp(0, S_max - 1)
+    assert pos.numel() in (1, B), positions.shape
+    pos = pos.expand(B)
+    if k_new is not None:
+        bidx = torch.arange(B, device=q.device)
+        k_cache[bidx, :, pos] = k_new.to(k_cache.dtype)
+        v_cache[bidx, :, pos] = v_new.to(v_cache.dtype)
+    dead = torch.arange(S_max, device=q.device)[None, :] > pos[:, None]
+    scores = torch.einsum("bhd,bhsd->bhs", q.float(), k_cache.float()) * scale
+    scores = scores.masked_fill(dead[:, None, :], float("-inf"))
+    p = torch.softmax(scores, dim=-1)
+    v32 = v_cache.float().masked_fill(dead[:, None, :, None], 0.0)
+    return torch.einsum("bhs,bhsd->bhd", p, v32).to(q.dtype)
+
+
 # --------------------------------------------------------------------------
 # Embedding
 # --------------------------------------------------------------------------
