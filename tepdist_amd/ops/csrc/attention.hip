@@ -3,30 +3,43 @@
 // the reference leaves attention to XLA codegen); docs/KERNELS.md has the
 // full design discussion.
 //
-// Forward: one block = 256 q-rows, 8 waves x 32 q columns sharing the
-// double-buffered K/V staging. Scores are computed TRANSPOSED
-// (S^T = mfma(K, Q)) so softmax state is per-lane (two shfl_xor per
-// reduction) and P^T feeds the PV MFMA straight from the accumulators via
-// the k-permutation invariance; O accumulates as O^T and scatters once.
-// Saves per-row logsumexp; the S x S score matrix never touches HBM.
+// Forward: one block = 512 q rows (D=128: 256), 8 waves sharing the
+// double-buffered K/V staging; at D=64 wave w owns the 32-row pairs w and
+// 15-w so the causal mask leaves every wave the same work. Scores are
+// computed TRANSPOSED (S^T = mfma(K, Q)) so softmax state is per-lane (two
+// shfl_xor per reduction) and P^T feeds the PV MFMA straight from the
+// accumulators via the k-permutation invariance; O accumulates as O^T and
+// scatters once. Saves per-row logsumexp; the S x S score matrix never
+// touches HBM.
 //
 // Backward: TWO atomics-free kernels (the classic fused flash2 backward
 // spends most of its time on dQ atomicAdd traffic — measured with the
 // section probe, see profiles/):
-//   - dK/dV kernel: block = 128 kv rows (8 waves x 16-kv slices sharing
-//     the Q/dO tile staging); S = mfma(Q, K) untransposed puts kv in the
-//     lane index so dV^T/dK^T consume P/dS from the accumulators
-//     (k-permuted) against v_perm-transposed dO^T/Q^T images.
-//   - dQ kernel: forward-shaped, dQ^T accumulated in registers, bf16
-//     output written directly in the packed-qkv strided layout.
+//   - dK/dV kernel: block = 256 kv rows (D=128: 128) as 128-row slabs, 8
+//     waves x 16-kv slices sharing the Q/dO tile staging; S = mfma(Q, K)
+//     untransposed puts kv in the lane index so dV^T/dK^T consume P/dS from
+//     the accumulators (k-permuted). Slices wholly above the causal
+//     diagonal of a q tile are skipped.
+//   - dQ kernel: forward-shaped (same pair ownership), dQ^T accumulated in
+//     registers, bf16 output written directly in the packed-qkv strided
+//     layout.
 // delta = rowsum(dO*O) is the flash2 preprocess.
+//
+// Every streamed tile (K, V, Q, dO) is fetched once with 16B row loads and
+// kept as ONE natural [rows][D] LDS image. The products that need it
+// transposed (V^T in fwd, dO^T/Q^T in dK/dV, K^T in dQ) form their
+// A-fragments at read time with ds_read_b64_tr_b16 (tr_frag, lds_frag.h).
+// Row constants are folded: every P is exp2 of one fma with scale*log2e
+// (fwd: -m*log2e per lane; backward: -lse*log2e), dS is formed without
+// `scale`, and `scale` is applied once to the dK/dQ accumulators at the
+// store.
 
 #include <algorithm>
-#include <cstdlib>
 #include <stdexcept>
 
 #include "common.h"
 #include "kernels.h"
+#include "lds_frag.h"
 
 namespace tepdist {
 
@@ -36,20 +49,12 @@ constexpr int NT = 256;
 constexpr int QB = 128;   // q rows per block (fwd)
 constexpr int KB = 64;    // kv rows per tile
 
-// LDS addressing for a [rows][C] bf16 image, C in {64,128}: XOR swizzle of
-// the 16B column slot by bit-reversed (row>>1) (see gemm.hip).
-template <int C>
-DEV_INLINE int loff(int row, int col_e) {
-  const int r1 = row >> 1;
-  const int x = ((r1 & 1) << 2) | (r1 & 2) | ((r1 >> 2) & 1);
-  return row * C + (col_e ^ ((x << 3) & (C - 1)));
-}
-
 // branchless exp: one v_exp_f32, no libcall special-casing. Arguments are
 // always <= 0 here (running-max subtraction / masked to -3e38), so the only
 // edge is underflow to 0 — exactly what the hardware instruction does.
+constexpr float kLog2e = 1.4426950408889634f;
 DEV_INLINE float fast_exp(float x) {
-  return __builtin_amdgcn_exp2f(x * 1.4426950408889634f);
+  return __builtin_amdgcn_exp2f(x * kLog2e);
 }
 
 // execution barrier with LDS-visibility only: s_waitcnt lgkmcnt(0) then a
@@ -86,8 +91,8 @@ DEV_INLINE float warp16_sum(float v) {
 // the MFMA k-permutation invariance (a consistent reorder of the k slots of
 // both operands leaves the dot product unchanged): B slot (g, e) holds
 // kv = 32c + 4g + e (e<4, from C-frag 2c) or 32c + 16 + 4g + (e-4) (from
-// C-frag 2c+1), and the A operand (V^T, staged [D][KB] in LDS) is read with
-// the same kv order as two 8B vectors. O accumulates transposed ([d][q],
+// C-frag 2c+1), and the A operand (V^T, from the natural [KB][D] image) is read with
+// the same kv order by two transposed 8B reads. O accumulates transposed ([d][q],
 // q = lane&15 — the same lane as the softmax state, so the alpha rescale is
 // a per-lane multiply) and is scattered once at the end. No P tile ever
 // touches LDS.
@@ -99,6 +104,16 @@ constexpr int NTF = 512;   // 8 waves x 64 q columns (QBF = 512): the
                            // 64 q are processed as two sequential 16-q
                            // pairs so the score accumulators stay [4][2]
 constexpr int QBF = 512;   // D=64; D=128 uses 256 (register budget)
+
+// First q row of the hp-th 32-row pair of a wave (fwd and dQ kernels).
+// NQ=4 (D=64): the block's 16 pairs are dealt so that wave w owns pairs w
+// and 15-w — under the causal mask pair p has work in ceil((32p+32)/64) kv
+// tiles, so every wave gets the same total and no SIMD idles at the per-tile
+// barrier while wave 7 finishes. NQ=2 (D=128): one pair per wave, in order.
+template <int NQ>
+DEV_INLINE int pair_row0(int q0, int wave, int hp) {
+  return NQ == 4 ? q0 + 32 * (hp ? 15 - wave : wave) : q0 + 32 * wave;
+}
 
 template <int D, int NQ = (D == 64 ? 4 : 2)>  // 16-q groups per wave
 __launch_bounds__(NTF) __global__
@@ -113,10 +128,9 @@ void flash_fwd_kernel(const bf16_t* __restrict__ Q,
   const int bh = blockIdx.y;
   const int b = bh / H, h = bh % H;
   const int q0 = blockIdx.x * (128 * NQ);   // 8 waves x 16*NQ q rows
-  const int wave = threadIdx.x >> 6;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   const int g = lane >> 4;
-  const int wq0 = q0 + wave * 16 * NQ;   // this wave's q columns
 
   const bf16_t* qp = Q + (int64_t)b * q_bs + (int64_t)h * q_hs;
   const bf16_t* kp = K + (int64_t)b * q_bs + (int64_t)h * q_hs;
@@ -125,8 +139,8 @@ void flash_fwd_kernel(const bf16_t* __restrict__ Q,
 
   // double-buffered tiles: compute reads parity (t&1) while the staging
   // writes parity ^1 — one barrier per tile instead of two
-  __shared__ bf16_t smem[2 * (KB * D + D * KB)];
-  const int BUFSZ = KB * D + D * KB;
+  __shared__ __attribute__((aligned(16))) bf16_t smem[2 * 2 * KB * D];
+  const int BUFSZ = 2 * KB * D;   // K and V, both natural [KB][D]
 
   // Q fragments (PV B-layout twin): nf-th 16-q group, kk-th 32-d chunk
   bf16x8 qf[NQ][DK];
@@ -134,7 +148,8 @@ void flash_fwd_kernel(const bf16_t* __restrict__ Q,
   for (int nf = 0; nf < NQ; ++nf)
 #pragma unroll
     for (int kk = 0; kk < DK; ++kk) {
-      const int row = wq0 + nf * 16 + (lane & 15);
+      const int row = pair_row0<NQ>(q0, wave, nf >> 1) + (nf & 1) * 16 +
+                      (lane & 15);
       bf16x8 v8 = {};
       if (row < S)
         v8 = *reinterpret_cast<const bf16x8*>(
@@ -142,6 +157,7 @@ void flash_fwd_kernel(const bf16_t* __restrict__ Q,
       qf[nf][kk] = v8;
     }
 
+  const float sl2 = scale * kLog2e;
   f32x4 acc_o[DF][NQ] = {};   // O^T: d = 16*df + 4g + e, q = lane&15 (+16nf)
   float m_r[NQ], l_r[NQ];
 #pragma unroll
@@ -150,14 +166,11 @@ void flash_fwd_kernel(const bf16_t* __restrict__ Q,
     l_r[i] = 0.f;
   }
 
-  // staging registers (issue-early / write-late split):
-  // K: KUN x 16B per thread; V: 8 x 4B per slab (v_perm transpose slabs;
-  // (KB/8)*(D/2) slabs total — more than one per thread when D = 128)
+  // staging registers (issue-early / write-late split): K and V rows as
+  // KUN x 16B per thread each. V^T fragments are formed at read time
+  // (tr_frag), so V needs no second fetch and no transposed image.
   constexpr int KUN = KB * D / 8 / NTF;
-  constexpr int NSLAB = (KB / 8) * (D / 2);
-  constexpr int SUN = (NSLAB + NTF - 1) / NTF;
-  bf16x8 krg[KUN];
-  uint32_t vrg[SUN][8];
+  bf16x8 krg[KUN], vrg[KUN];
 
   auto stage_load = [&](int kv0) {
 #pragma unroll
@@ -165,56 +178,27 @@ void flash_fwd_kernel(const bf16_t* __restrict__ Q,
       const int idx = threadIdx.x + u * NTF;
       const int row = idx / (D / 8);
       const int c = (idx % (D / 8)) * 8;
-      bf16x8 v8 = {};
-      if (kv0 + row < S)
-        v8 = *reinterpret_cast<const bf16x8*>(
+      bf16x8 k8 = {}, v8 = {};   // rows >= S stay zero (pad, don't mask)
+      if (kv0 + row < S) {
+        k8 = *reinterpret_cast<const bf16x8*>(
             kp + (int64_t)(kv0 + row) * q_rs + c);
-      krg[u] = v8;
-    }
-#pragma unroll
-    for (int u = 0; u < SUN; ++u) {
-      const int idx = threadIdx.x + u * NTF;
-      if (idx >= NSLAB) break;
-      const int f = 2 * (idx % (D / 2));
-      const int kb = idx / (D / 2);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int kv = kv0 + kb * 8 + j;
-        bf16x2 v2 = {};
-        if (kv < S)
-          v2 = *reinterpret_cast<const bf16x2*>(vp + (int64_t)kv * q_rs + f);
-        vrg[u][j] = __builtin_bit_cast(uint32_t, v2);
+        v8 = *reinterpret_cast<const bf16x8*>(
+            vp + (int64_t)(kv0 + row) * q_rs + c);
       }
+      krg[u] = k8;
+      vrg[u] = v8;
     }
   };
   auto stage_write = [&](int buf) {
     bf16_t* sK = smem + buf * BUFSZ;
-    bf16_t* sVT = sK + KB * D;
+    bf16_t* sV = sK + KB * D;
 #pragma unroll
     for (int u = 0; u < KUN; ++u) {
       const int idx = threadIdx.x + u * NTF;
       const int row = idx / (D / 8);
       const int c = (idx % (D / 8)) * 8;
       *reinterpret_cast<bf16x8*>(sK + loff<D>(row, c)) = krg[u];
-    }
-#pragma unroll
-    for (int u = 0; u < SUN; ++u) {
-      const int idx = threadIdx.x + u * NTF;
-      if (idx >= NSLAB) break;
-      const int f = 2 * (idx % (D / 2));
-      const int kb = idx / (D / 2);
-      uint32_t o0[4], o1[4];
-#pragma unroll
-      for (int d2 = 0; d2 < 4; ++d2) {
-        o0[d2] = __builtin_amdgcn_perm(vrg[u][2 * d2 + 1], vrg[u][2 * d2],
-                                       0x05040100u);
-        o1[d2] = __builtin_amdgcn_perm(vrg[u][2 * d2 + 1], vrg[u][2 * d2],
-                                       0x07060302u);
-      }
-      *reinterpret_cast<uint4*>(sVT + loff<KB>(f, kb * 8)) =
-          make_uint4(o0[0], o0[1], o0[2], o0[3]);
-      *reinterpret_cast<uint4*>(sVT + loff<KB>(f + 1, kb * 8)) =
-          make_uint4(o1[0], o1[1], o1[2], o1[3]);
+      *reinterpret_cast<bf16x8*>(sV + loff<D>(row, c)) = vrg[u];
     }
   };
 
@@ -225,13 +209,14 @@ void flash_fwd_kernel(const bf16_t* __restrict__ Q,
   int t = 0;
   for (int kv0 = 0; kv0 < kv_end; kv0 += KB, ++t) {
     const bf16_t* sK = smem + (t & 1) * BUFSZ;
-    const bf16_t* sVT = sK + KB * D;
+    const bf16_t* sV = sK + KB * D;
     if (kv0 + KB < kv_end) stage_load(kv0 + KB);  // overlap with compute
 
-    if (!causal || kv0 <= wq0 + 16 * NQ - 1) {  // wave has unmasked work
+    // wave has unmasked work (its last pair is its lowest one)
+    if (!causal || kv0 <= pair_row0<NQ>(q0, wave, NQ / 2 - 1) + 31) {
 #pragma unroll
       for (int hp = 0; hp < NQ / 2; ++hp) {  // sequential 32-q pairs
-        const int pq0 = wq0 + 32 * hp;
+        const int pq0 = pair_row0<NQ>(q0, wave, hp);
         if (causal && kv0 > pq0 + 31) continue;  // pair fully masked
         // --- S^T = K Q^T: kv = 16*mi + 4g + e, q = lane&15 + 16*nf ---
         f32x4 st[4][2] = {};
@@ -248,9 +233,12 @@ void flash_fwd_kernel(const bf16_t* __restrict__ Q,
                   kf, qf[2 * hp + nf][kk], st[mi][nf], 0, 0, 0);
           }
         __builtin_amdgcn_s_setprio(0);
-        // --- scale + mask; online softmax (per-lane q state). Tiles
-        // fully inside the causal triangle and the sequence skip the
-        // per-element mask selects (wave-uniform branch) ---
+        // --- mask; online softmax (per-lane q state) on the RAW scores:
+        // scale > 0, so the row max is taken before scaling and
+        // p = exp2(s * (scale*log2e) - m*log2e) is one fma per element;
+        // m_r / l_r / LSE stay in scaled natural-log units. Tiles fully
+        // inside the causal triangle and the sequence skip the per-element
+        // mask selects (wave-uniform branch) ---
         const bool inner = kv0 + KB <= pq0 && kv0 + KB <= S &&
                            pq0 + 32 <= S;
 #pragma unroll
@@ -262,11 +250,8 @@ void flash_fwd_kernel(const bf16_t* __restrict__ Q,
 #pragma unroll
             for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                const float sv = st[mi][nf][e] * scale;
-                st[mi][nf][e] = sv;
-                tmax = fmaxf(tmax, sv);
-              }
+              for (int e = 0; e < 4; ++e)
+                tmax = fmaxf(tmax, st[mi][nf][e]);
           } else {
 #pragma unroll
             for (int mi = 0; mi < 4; ++mi)
@@ -275,23 +260,26 @@ void flash_fwd_kernel(const bf16_t* __restrict__ Q,
                 const int kg = kv0 + mi * 16 + 4 * g + e;
                 const bool masked = (causal && kg > qg) || kg >= S ||
                                     qg >= S;
-                const float sv = masked ? -3.0e38f : st[mi][nf][e] * scale;
+                const float sv = masked ? -3.0e38f : st[mi][nf][e];
                 st[mi][nf][e] = sv;
                 tmax = fmaxf(tmax, sv);
               }
           }
           tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
           tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-          const float mn = fmaxf(m_r[nfg], tmax);
+          const float mn = fmaxf(m_r[nfg], tmax * scale);
           const float alpha = fast_exp(m_r[nfg] - mn);
           m_r[nfg] = mn;
+          const float nm2 = -mn * kLog2e;
           float rs = 0.f;
 #pragma unroll
           for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-              // sv - mn <= 0 always; fully-masked rows give -inf -> 0
-              const float p = fast_exp(st[mi][nf][e] - mn);
+              // s*scale - mn <= 0 always; masked elements (-3e38)
+              // underflow to 0
+              const float p = __builtin_amdgcn_exp2f(
+                  __builtin_fmaf(st[mi][nf][e], sl2, nm2));
               st[mi][nf][e] = p;
               rs += p;
             }
@@ -317,16 +305,7 @@ void flash_fwd_kernel(const bf16_t* __restrict__ Q,
             }
 #pragma unroll
           for (int df = 0; df < DF; ++df) {
-            const bf16x4 v0 = *reinterpret_cast<const bf16x4*>(
-                sVT + loff<KB>(16 * df + (lane & 15), 32 * c + 4 * g));
-            const bf16x4 v1 = *reinterpret_cast<const bf16x4*>(
-                sVT + loff<KB>(16 * df + (lane & 15), 32 * c + 16 + 4 * g));
-            bf16x8 vfr;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              vfr[e] = v0[e];
-              vfr[e + 4] = v1[e];
-            }
+            const bf16x8 vfr = tr_frag<D>(sV, c, df, lane);
 #pragma unroll
             for (int nf = 0; nf < 2; ++nf)
               acc_o[df][2 * hp + nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
@@ -343,7 +322,8 @@ void flash_fwd_kernel(const bf16_t* __restrict__ Q,
   // --- epilogue: O = O^T^T / l, write O and lse ---
 #pragma unroll
   for (int nf = 0; nf < NQ; ++nf) {
-    const int qg = wq0 + nf * 16 + (lane & 15);
+    const int qg = pair_row0<NQ>(q0, wave, nf >> 1) + (nf & 1) * 16 +
+                   (lane & 15);
     if (qg >= S) continue;
     const float lv = l_r[nf];
     const float inv = (lv > 0.f) ? 1.0f / lv : 0.f;
@@ -413,53 +393,6 @@ void flash_bwd_delta_kernel(const bf16_t* __restrict__ dO,
   }
 }
 
-// cooperative stage of a [T][D] tile as BOTH natural [T][D] and transposed
-// [D][T] images (v_perm 8x2 slabs for the transpose)
-template <int T, int D>
-DEV_INLINE void stage_nat_t(const bf16_t* __restrict__ src, int row0, int S,
-                            int64_t rs, bf16_t* nat, bf16_t* tr) {
-  constexpr int UN = T * D / 8 / NT;
-#pragma unroll
-  for (int u = 0; u < UN; ++u) {
-    const int idx = threadIdx.x + u * NT;
-    const int row = idx / (D / 8);
-    const int c = (idx % (D / 8)) * 8;
-    bf16x8 v8 = {};
-    if (row0 + row < S)
-      v8 = *reinterpret_cast<const bf16x8*>(
-          src + (int64_t)(row0 + row) * rs + c);
-    *reinterpret_cast<bf16x8*>(nat + loff<D>(row, c)) = v8;
-  }
-  constexpr int NSLAB = (T / 8) * (D / 2);
-#pragma unroll
-  for (int u = 0; u < (NSLAB + NT - 1) / NT; ++u) {
-    const int idx = threadIdx.x + u * NT;
-    if (idx < NSLAB) {
-      const int f = 2 * (idx % (D / 2));
-      const int kb = idx / (D / 2);
-      uint32_t r[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int row = row0 + kb * 8 + j;
-        bf16x2 v2 = {};
-        if (row < S)
-          v2 = *reinterpret_cast<const bf16x2*>(src + (int64_t)row * rs + f);
-        r[j] = __builtin_bit_cast(uint32_t, v2);
-      }
-      uint32_t o0[4], o1[4];
-#pragma unroll
-      for (int d2 = 0; d2 < 4; ++d2) {
-        o0[d2] = __builtin_amdgcn_perm(r[2 * d2 + 1], r[2 * d2], 0x05040100u);
-        o1[d2] = __builtin_amdgcn_perm(r[2 * d2 + 1], r[2 * d2], 0x07060302u);
-      }
-      *reinterpret_cast<uint4*>(tr + loff<T>(f, kb * 8)) =
-          make_uint4(o0[0], o0[1], o0[2], o0[3]);
-      *reinterpret_cast<uint4*>(tr + loff<T>(f + 1, kb * 8)) =
-          make_uint4(o1[0], o1[1], o1[2], o1[3]);
-    }
-  }
-}
-
 // Backward is TWO kernels, each free of global atomics (a single-kernel
 // flash2 backward accumulates dQ with atomicAdd: 16 read-modify-write
 // passes over an fp32 image dominated the measured time — see
@@ -469,8 +402,8 @@ DEV_INLINE void stage_nat_t(const bf16_t* __restrict__ src, int row0, int S,
 // 16-kv slice kv = kv0 + 16w + (lane&15) and iterates q tiles of 64.
 // Scores are computed UNtransposed, S = mfma(Q, K), so dV^T and dK^T
 // consume P and dS directly from the accumulators as B-fragments via the
-// MFMA k-permutation invariance against transpose-staged dO^T / Q^T
-// A-operands — P and dS never touch LDS. dK/dV accumulate transposed in
+// MFMA k-permutation invariance against dO^T / Q^T A-operands read
+// transposed from the natural tile images — P and dS never touch LDS. dK/dV accumulate transposed in
 // registers across all q tiles and scatter once.
 constexpr int NTA = 512;   // 8 waves; each wave owns one 16-kv slice per
                            // 128-kv slab (KBA/128 slabs per block: the q/dO
@@ -478,7 +411,7 @@ constexpr int NTA = 512;   // 8 waves; each wave owns one 16-kv slice per
                            // every slab — the backward's staging VALU was
                            // the measured bound, profiles/flash_bwd_pmc_r2)
 
-template <int D, int PROBE = 0, int KBA = (D == 64 ? 256 : 128)>
+template <int D, int KBA = (D == 64 ? 256 : 128)>
 __launch_bounds__(NTA) __global__
 void flash_bwd_kv_kernel(const bf16_t* __restrict__ Q,
                          const bf16_t* __restrict__ K,
@@ -497,7 +430,7 @@ void flash_bwd_kv_kernel(const bf16_t* __restrict__ Q,
   const int bh = blockIdx.y;
   const int b = bh / H, h = bh % H;
   const int kv0 = blockIdx.x * KBA;
-  const int wave = threadIdx.x >> 6;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   const int g = lane >> 4;
 
@@ -508,14 +441,22 @@ void flash_bwd_kv_kernel(const bf16_t* __restrict__ Q,
   const bf16_t* vp = V + qoff;
   const bf16_t* dop = dO + ooff;
 
-  __shared__ bf16_t smem[KBA * D * 2 + QT * D * 2 + D * QT * 2];
-  bf16_t* sKb = smem;                       // [KB][D] natural
-  bf16_t* sVb = sKb + KBA * D;               // [KB][D] natural
-  bf16_t* sQ = sVb + KBA * D;                // [QT][D] natural
-  bf16_t* sQT = sQ + QT * D;                // [D][QT]
-  bf16_t* sdO = sQT + D * QT;               // [QT][D] natural
-  bf16_t* sdOT = sdO + QT * D;              // [D][QT]
-  __shared__ float sLSE[QT], sDELTA[QT];
+  // one natural image per operand: sQ/sdO are read by rows for S/dP and
+  // transposed (tr_frag) for dK^T/dV^T
+  __shared__ __attribute__((aligned(16))) bf16_t
+      smem[KBA * D * 2 + QT * D * 2];
+  bf16_t* sKb = smem;                       // [KBA][D]
+  bf16_t* sVb = sKb + KBA * D;              // [KBA][D]
+  bf16_t* sQ = sVb + KBA * D;               // [QT][D]
+  bf16_t* sdO = sQ + QT * D;                // [QT][D]
+  // per-row constants of the q tile: sNL2 = -lse*log2e (-3e38 where the
+  // row has no lse) so P = exp2(S * scale*log2e + nl2) is one fma per
+  // element, and delta; dS is formed without `scale`, which is applied once
+  // to the dK accumulators. (Seeding the S/dP accumulators with the row
+  // constants instead measured slower here: q sits on the element index,
+  // so every slab pays 8 more LDS reads ahead of its MFMA chains.)
+  __shared__ __attribute__((aligned(16))) float sNL2[QT], sDELTA[QT];
+  const float sl2 = scale * kLog2e;
 
   // stage K, V tiles (fixed for the block; natural layout only)
   {
@@ -546,10 +487,7 @@ void flash_bwd_kv_kernel(const bf16_t* __restrict__ Q,
 
   // issue-early / write-late staging registers for the Q and dO tiles
   constexpr int QUN = QT * D / 8 / NTA;
-  constexpr int TSLAB = (QT / 8) * (D / 2);   // v_perm transpose slabs
-  constexpr int TUN = (TSLAB + NTA - 1) / NTA;
   bf16x8 qn[QUN], don[QUN];
-  uint32_t qt[TUN][8], dot_[TUN][8];
   float lse2[QT / NTA + 1], dl2[QT / NTA + 1];
 
   auto tile_load = [&](int q0) {
@@ -568,29 +506,10 @@ void flash_bwd_kv_kernel(const bf16_t* __restrict__ Q,
       qn[u] = a;
       don[u] = b2;
     }
-#pragma unroll
-    for (int u = 0; u < TUN; ++u) {
-      const int idx = threadIdx.x + u * NTA;
-      if (idx >= TSLAB) break;
-      const int f = 2 * (idx % (D / 2));
-      const int kb = idx / (D / 2);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int row = q0 + kb * 8 + j;
-        bf16x2 a = {}, b2 = {};
-        if (row < S) {
-          a = *reinterpret_cast<const bf16x2*>(
-              qp + (int64_t)row * q_rs + f);
-          b2 = *reinterpret_cast<const bf16x2*>(
-              dop + (int64_t)row * o_rs + f);
-        }
-        qt[u][j] = __builtin_bit_cast(uint32_t, a);
-        dot_[u][j] = __builtin_bit_cast(uint32_t, b2);
-      }
-    }
     for (int i = threadIdx.x, s2 = 0; i < QT; i += NTA, ++s2) {
       const int qg = q0 + i;
-      lse2[s2] = (qg < S) ? LSE[(int64_t)bh * S + qg] : -3.0e38f;
+      const float l = (qg < S) ? LSE[(int64_t)bh * S + qg] : -3.0e38f;
+      lse2[s2] = (l > -1.0e38f) ? -l * kLog2e : -3.0e38f;
       dl2[s2] = (qg < S) ? DELTA[(int64_t)bh * S + qg] : 0.f;
     }
   };
@@ -603,38 +522,8 @@ void flash_bwd_kv_kernel(const bf16_t* __restrict__ Q,
       *reinterpret_cast<bf16x8*>(sQ + loff<D>(row, c)) = qn[u];
       *reinterpret_cast<bf16x8*>(sdO + loff<D>(row, c)) = don[u];
     }
-#pragma unroll
-    for (int u = 0; u < TUN; ++u) {
-      const int idx = threadIdx.x + u * NTA;
-      if (idx >= TSLAB) break;
-      const int f = 2 * (idx % (D / 2));
-      const int kb = idx / (D / 2);
-      uint32_t o0[4], o1[4];
-#pragma unroll
-      for (int d2 = 0; d2 < 4; ++d2) {
-        o0[d2] = __builtin_amdgcn_perm(qt[u][2 * d2 + 1], qt[u][2 * d2],
-                                       0x05040100u);
-        o1[d2] = __builtin_amdgcn_perm(qt[u][2 * d2 + 1], qt[u][2 * d2],
-                                       0x07060302u);
-      }
-      *reinterpret_cast<uint4*>(sQT + loff<QT>(f, kb * 8)) =
-          make_uint4(o0[0], o0[1], o0[2], o0[3]);
-      *reinterpret_cast<uint4*>(sQT + loff<QT>(f + 1, kb * 8)) =
-          make_uint4(o1[0], o1[1], o1[2], o1[3]);
-#pragma unroll
-      for (int d2 = 0; d2 < 4; ++d2) {
-        o0[d2] = __builtin_amdgcn_perm(dot_[u][2 * d2 + 1], dot_[u][2 * d2],
-                                       0x05040100u);
-        o1[d2] = __builtin_amdgcn_perm(dot_[u][2 * d2 + 1], dot_[u][2 * d2],
-                                       0x07060302u);
-      }
-      *reinterpret_cast<uint4*>(sdOT + loff<QT>(f, kb * 8)) =
-          make_uint4(o0[0], o0[1], o0[2], o0[3]);
-      *reinterpret_cast<uint4*>(sdOT + loff<QT>(f + 1, kb * 8)) =
-          make_uint4(o1[0], o1[1], o1[2], o1[3]);
-    }
     for (int i = threadIdx.x, s2 = 0; i < QT; i += NTA, ++s2) {
-      sLSE[i] = lse2[s2];
+      sNL2[i] = lse2[s2];
       sDELTA[i] = dl2[s2];
     }
   };
@@ -648,6 +537,10 @@ void flash_bwd_kv_kernel(const bf16_t* __restrict__ Q,
 
 #pragma unroll
     for (int sl = 0; sl < NSL; ++sl) {
+      // this wave's 16-kv slice lies wholly above the diagonal of the q
+      // tile: every P and dS would be zero (wave-uniform; no barrier in
+      // the slab body)
+      if (causal && kv0 + sl * 128 + wave * 16 > q0 + QT - 1) continue;
       // S = Q K^T ; dP = dO V^T  — C-frags: q = 16mi+4g+e, kv = lane&15
       f32x4 st[4] = {};
       f32x4 dpt[4] = {};
@@ -679,19 +572,20 @@ void flash_bwd_kv_kernel(const bf16_t* __restrict__ Q,
       const bool winner = (!causal || kvb + wave * 16 + 15 < q0) &&
                           q0 + QT <= S && kvb + 128 <= S;
       if (winner) {
-        f32x4 lsev[4], dlv[4];
+        f32x4 nl2v[4], dlv[4];
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi) {
-          lsev[mi] = *reinterpret_cast<const f32x4*>(sLSE + 16 * mi + 4 * g);
+          nl2v[mi] = *reinterpret_cast<const f32x4*>(sNL2 + 16 * mi + 4 * g);
           dlv[mi] = *reinterpret_cast<const f32x4*>(sDELTA + 16 * mi + 4 * g);
         }
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            const float pt = fast_exp(st[mi][e] * scale - lsev[mi][e]);
-            st[mi][e] = pt;
-            dpt[mi][e] = pt * (dpt[mi][e] - dlv[mi][e]) * scale;
+            const float pt = __builtin_amdgcn_exp2f(
+                __builtin_fmaf(st[mi][e], sl2, nl2v[mi][e]));
+            st[mi][e] = pt;                              // now P
+            dpt[mi][e] = pt * (dpt[mi][e] - dlv[mi][e]); // now dS / scale
           }
       } else {
 #pragma unroll
@@ -700,14 +594,15 @@ void flash_bwd_kv_kernel(const bf16_t* __restrict__ Q,
           for (int e = 0; e < 4; ++e) {
             const int qrow = 16 * mi + 4 * g + e;
             const int qg = q0 + qrow;
-            const float lse = sLSE[qrow];
+            const float nl2 = sNL2[qrow];
             const float dl = sDELTA[qrow];
             const bool valid = qg < S && kvg < S && (!causal || kvg <= qg) &&
-                               lse > -1.0e38f;
-            const float arg = valid ? st[mi][e] * scale - lse : -3.0e38f;
-            const float pt = fast_exp(arg);              // select, not branch
-            st[mi][e] = pt;                              // now P
-            dpt[mi][e] = pt * (dpt[mi][e] - dl) * scale; // now dS
+                               nl2 > -1.0e38f;
+            const float arg =
+                valid ? __builtin_fmaf(st[mi][e], sl2, nl2) : -3.0e38f;
+            const float pt = __builtin_amdgcn_exp2f(arg);  // select, not branch
+            st[mi][e] = pt;                        // now P
+            dpt[mi][e] = pt * (dpt[mi][e] - dl);   // now dS / scale
           }
       }
 
@@ -725,26 +620,8 @@ void flash_bwd_kv_kernel(const bf16_t* __restrict__ Q,
         }
 #pragma unroll
         for (int df = 0; df < DF; ++df) {
-          // PROBE=1: broadcast row (conflict-free, WRONG numerics) — an
-          // upper-bound timing probe for the bank-conflict cost of these
-          // reads (benchmarks/prof_attn.py probe mode)
-          const int fr = PROBE ? 0 : (lane & 15);
-          const bf16x4 a0 = *reinterpret_cast<const bf16x4*>(
-              sdOT + loff<QT>(16 * df + fr, 32 * c + 4 * g));
-          const bf16x4 a1 = *reinterpret_cast<const bf16x4*>(
-              sdOT + loff<QT>(16 * df + fr, 32 * c + 16 + 4 * g));
-          const bf16x4 q0f = *reinterpret_cast<const bf16x4*>(
-              sQT + loff<QT>(16 * df + fr, 32 * c + 4 * g));
-          const bf16x4 q1f = *reinterpret_cast<const bf16x4*>(
-              sQT + loff<QT>(16 * df + fr, 32 * c + 16 + 4 * g));
-          bf16x8 afr, qfr;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            afr[e] = a0[e];
-            afr[e + 4] = a1[e];
-            qfr[e] = q0f[e];
-            qfr[e + 4] = q1f[e];
-          }
+          const bf16x8 afr = tr_frag<D>(sdO, c, df, lane);
+          const bf16x8 qfr = tr_frag<D>(sQ, c, df, lane);
           acc_dvT[sl][df] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
               afr, pb, acc_dvT[sl][df], 0, 0, 0);
           acc_dkT[sl][df] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
@@ -753,7 +630,7 @@ void flash_bwd_kv_kernel(const bf16_t* __restrict__ Q,
       }
       __builtin_amdgcn_s_setprio(0);
     }
-    BAR_LDS();  // sQ/sQT/sdO/sdOT reads retired
+    BAR_LDS();  // sQ/sdO reads retired
     if (q0 + QT < S) {
       tile_write();
       BAR_LDS();  // next tile's images visible
@@ -770,7 +647,7 @@ void flash_bwd_kv_kernel(const bf16_t* __restrict__ Q,
         bf16x4 kv4, vv4;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          kv4[e] = f2bf(acc_dkT[sl][df][e]);
+          kv4[e] = f2bf(acc_dkT[sl][df][e] * scale);
           vv4[e] = f2bf(acc_dvT[sl][df][e]);
         }
         const int64_t off = qoff + (int64_t)kvg * q_rs + 16 * df + 4 * g;
@@ -784,8 +661,8 @@ void flash_bwd_kv_kernel(const bf16_t* __restrict__ Q,
 // Kernel B (dQ): forward-shaped — one block = 128 q rows, wave w owns 32 q
 // columns, iterates kv tiles; dQ accumulates TRANSPOSED in registers
 // ([d][q], q = lane&15 like the fwd O^T accumulator) with dS^T consumed
-// straight from the accumulators (k-permutation) against a
-// transpose-staged K^T — no LDS scatter, no atomics, bf16 output written
+// straight from the accumulators (k-permutation) against K^T read
+// transposed from the natural K image — no LDS scatter, no atomics, bf16 output written
 // directly (strided; serves the packed-qkv layout too).
 constexpr int NTB = 512;   // 8 waves; D=64 blocks take 512 q (two
                            // sequential 32-q pairs per wave — the same
@@ -810,10 +687,9 @@ void flash_bwd_dq_kernel(const bf16_t* __restrict__ Q,
   const int bh = blockIdx.y;
   const int b = bh / H, h = bh % H;
   const int q0 = blockIdx.x * (128 * NQ);
-  const int wave = threadIdx.x >> 6;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   const int g = lane >> 4;
-  const int wq0 = q0 + wave * 16 * NQ;
 
   const int64_t qoff = (int64_t)b * q_bs + (int64_t)h * q_hs;
   const int64_t ooff = (int64_t)b * o_bs + (int64_t)h * o_hs;
@@ -823,18 +699,26 @@ void flash_bwd_dq_kernel(const bf16_t* __restrict__ Q,
   const bf16_t* dop = dO + ooff;
   bf16_t* dqp = dQ + qoff;
 
-  __shared__ bf16_t smem[KB * D * 2 + D * KB];
-  bf16_t* sK = smem;                    // [KB][D] natural
-  bf16_t* sV = smem + KB * D;           // [KB][D] natural
-  bf16_t* sKT = sV + KB * D;            // [D][KB] (dQ^T A-operand)
+  __shared__ __attribute__((aligned(16))) bf16_t smem[KB * D * 2];
+  bf16_t* sK = smem;                    // [KB][D]; rows for S^T, tr_frag
+                                        // columns for the dQ^T A-operand
+  bf16_t* sV = smem + KB * D;           // [KB][D]
 
-  // Q and dO B-fragments + per-lane lse/delta (block-constant)
+  // Q and dO B-fragments + per-lane row constants (block-constant). q is
+  // the lane here, so the constants fold into one fma per element
+  // (P = exp2(s * scale*log2e + nl2_r), nl2_r = -lse*log2e, -3e38 where the
+  // row has no lse); seeding the MFMA accumulators with them costs 4
+  // registers per constant and spilled. `scale` is applied once to the dQ
+  // accumulators.
+  const float sl2 = scale * kLog2e;
   bf16x8 qf[NQ][DK], dof[NQ][DK];
-  float lse_r[NQ], dl_r[NQ];
+  float nl2_r[NQ], dl_r[NQ];
 #pragma unroll
   for (int nf = 0; nf < NQ; ++nf) {
-    const int row = wq0 + nf * 16 + (lane & 15);
-    lse_r[nf] = (row < S) ? LSE[(int64_t)bh * S + row] : -3.0e38f;
+    const int row = pair_row0<NQ>(q0, wave, nf >> 1) + (nf & 1) * 16 +
+                    (lane & 15);
+    const float l = (row < S) ? LSE[(int64_t)bh * S + row] : -3.0e38f;
+    nl2_r[nf] = (l > -1.0e38f) ? -l * kLog2e : -3.0e38f;
     dl_r[nf] = (row < S) ? DELTA[(int64_t)bh * S + row] : 0.f;
 #pragma unroll
     for (int kk = 0; kk < DK; ++kk) {
@@ -852,12 +736,9 @@ void flash_bwd_dq_kernel(const bf16_t* __restrict__ Q,
 
   f32x4 acc_dq[DF][NQ] = {};  // dQ^T: d = 16df+4g+e, q = lane&15 (+16nf)
 
-  // staging registers: K,V natural (16B each) + K^T v_perm slabs
+  // staging registers: K,V rows (16B each)
   constexpr int KUN = KB * D / 8 / NTB;
-  constexpr int NSLAB = (KB / 8) * (D / 2);
-  constexpr int SUN = (NSLAB + NTB - 1) / NTB;
   bf16x8 krg[KUN], vrg[KUN];
-  uint32_t ktr[SUN][8];
 
   auto stage_load = [&](int kv0) {
 #pragma unroll
@@ -875,21 +756,6 @@ void flash_bwd_dq_kernel(const bf16_t* __restrict__ Q,
       krg[u] = kv8;
       vrg[u] = vv8;
     }
-#pragma unroll
-    for (int u = 0; u < SUN; ++u) {
-      const int idx = threadIdx.x + u * NTB;
-      if (idx >= NSLAB) break;
-      const int f = 2 * (idx % (D / 2));
-      const int kb = idx / (D / 2);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int kv = kv0 + kb * 8 + j;
-        bf16x2 v2 = {};
-        if (kv < S)
-          v2 = *reinterpret_cast<const bf16x2*>(kp + (int64_t)kv * q_rs + f);
-        ktr[u][j] = __builtin_bit_cast(uint32_t, v2);
-      }
-    }
   };
   auto stage_write = [&]() {
 #pragma unroll
@@ -900,25 +766,6 @@ void flash_bwd_dq_kernel(const bf16_t* __restrict__ Q,
       *reinterpret_cast<bf16x8*>(sK + loff<D>(row, c)) = krg[u];
       *reinterpret_cast<bf16x8*>(sV + loff<D>(row, c)) = vrg[u];
     }
-#pragma unroll
-    for (int u = 0; u < SUN; ++u) {
-      const int idx = threadIdx.x + u * NTB;
-      if (idx >= NSLAB) break;
-      const int f = 2 * (idx % (D / 2));
-      const int kb = idx / (D / 2);
-      uint32_t o0[4], o1[4];
-#pragma unroll
-      for (int d2 = 0; d2 < 4; ++d2) {
-        o0[d2] = __builtin_amdgcn_perm(ktr[u][2 * d2 + 1], ktr[u][2 * d2],
-                                       0x05040100u);
-        o1[d2] = __builtin_amdgcn_perm(ktr[u][2 * d2 + 1], ktr[u][2 * d2],
-                                       0x07060302u);
-      }
-      *reinterpret_cast<uint4*>(sKT + loff<KB>(f, kb * 8)) =
-          make_uint4(o0[0], o0[1], o0[2], o0[3]);
-      *reinterpret_cast<uint4*>(sKT + loff<KB>(f + 1, kb * 8)) =
-          make_uint4(o1[0], o1[1], o1[2], o1[3]);
-    }
   };
 
   const int kv_end = causal ? min(S, q0 + 128 * NQ) : S;
@@ -928,10 +775,10 @@ void flash_bwd_dq_kernel(const bf16_t* __restrict__ Q,
   for (int kv0 = 0; kv0 < kv_end; kv0 += KB) {
     if (kv0 + KB < kv_end) stage_load(kv0 + KB);
 
-    if (!causal || kv0 <= wq0 + 16 * NQ - 1) {
+    if (!causal || kv0 <= pair_row0<NQ>(q0, wave, NQ / 2 - 1) + 31) {
 #pragma unroll
      for (int hp = 0; hp < NQ / 2; ++hp) {
-      const int pq0 = wq0 + 32 * hp;
+      const int pq0 = pair_row0<NQ>(q0, wave, hp);
       if (causal && kv0 > pq0 + 31) continue;
       // per 16-kv block: S^T = K Q^T and dP^T = V dO^T, then dS^T packed
       // to bf16 immediately (keeps only two f32x4 accumulator pairs live
@@ -965,9 +812,10 @@ void flash_bwd_dq_kernel(const bf16_t* __restrict__ Q,
           if (inner) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-              const float pt = fast_exp(st[nf][e] * scale - lse_r[nfg]);
+              const float pt = __builtin_amdgcn_exp2f(
+                  __builtin_fmaf(st[nf][e], sl2, nl2_r[nfg]));
               dsb[mi][nf][e] =
-                  f2bf(pt * (dpt[nf][e] - dl_r[nfg]) * scale);
+                  f2bf(pt * (dpt[nf][e] - dl_r[nfg]));   // dS / scale
             }
           } else {
 #pragma unroll
@@ -975,12 +823,13 @@ void flash_bwd_dq_kernel(const bf16_t* __restrict__ Q,
               const int kg = kv0 + 16 * mi + 4 * g + e;
               const bool valid = qg < S && kg < S &&
                                  (!causal || kg <= qg) &&
-                                 lse_r[nfg] > -1.0e38f;
-              const float arg = valid ? st[nf][e] * scale - lse_r[nfg]
-                                      : -3.0e38f;
-              const float pt = fast_exp(arg);
+                                 nl2_r[nfg] > -1.0e38f;
+              const float arg =
+                  valid ? __builtin_fmaf(st[nf][e], sl2, nl2_r[nfg])
+                        : -3.0e38f;
+              const float pt = __builtin_amdgcn_exp2f(arg);
               dsb[mi][nf][e] =
-                  f2bf(pt * (dpt[nf][e] - dl_r[nfg]) * scale);
+                  f2bf(pt * (dpt[nf][e] - dl_r[nfg]));   // dS / scale
             }
           }
         }
@@ -999,16 +848,7 @@ void flash_bwd_dq_kernel(const bf16_t* __restrict__ Q,
           }
 #pragma unroll
         for (int df = 0; df < DF; ++df) {
-          const bf16x4 k0 = *reinterpret_cast<const bf16x4*>(
-              sKT + loff<KB>(16 * df + (lane & 15), 32 * c + 4 * g));
-          const bf16x4 k1 = *reinterpret_cast<const bf16x4*>(
-              sKT + loff<KB>(16 * df + (lane & 15), 32 * c + 16 + 4 * g));
-          bf16x8 kfr;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            kfr[e] = k0[e];
-            kfr[e + 4] = k1[e];
-          }
+          const bf16x8 kfr = tr_frag<D>(sK, c, df, lane);
 #pragma unroll
           for (int nf = 0; nf < 2; ++nf)
             acc_dq[df][2 * hp + nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
@@ -1028,13 +868,14 @@ void flash_bwd_dq_kernel(const bf16_t* __restrict__ Q,
   // write dQ (transposed-accumulator scatter, bf16, strided layout)
 #pragma unroll
   for (int nf = 0; nf < NQ; ++nf) {
-    const int qg = wq0 + nf * 16 + (lane & 15);
+    const int qg = pair_row0<NQ>(q0, wave, nf >> 1) + (nf & 1) * 16 +
+                   (lane & 15);
     if (qg >= S) continue;
 #pragma unroll
     for (int df = 0; df < DF; ++df) {
       bf16x4 v4;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v4[e] = f2bf(acc_dq[df][nf][e]);
+      for (int e = 0; e < 4; ++e) v4[e] = f2bf(acc_dq[df][nf][e] * scale);
       *reinterpret_cast<bf16x4*>(
           dqp + (int64_t)qg * q_rs + 16 * df + 4 * g) = v4;
     }
@@ -1103,17 +944,6 @@ void attention_bwd_bf16(const void* q, const void* k, const void* v,
                        o_hs, o_rs);                                          \
     dim3 kgrid((S + (DD == 64 ? 255 : 127)) / (DD == 64 ? 256 : 128),       \
                B * H);                                                       \
-    static const bool kv_probe = std::getenv("TEPDIST_FLASH_PROBE");         \
-    if (kv_probe)                                                            \
-      hipLaunchKernelGGL((flash_bwd_kv_kernel<DD, 1>), kgrid, dim3(512), 0,  \
-                         stream, static_cast<const bf16_t*>(q),              \
-                         static_cast<const bf16_t*>(k),                      \
-                         static_cast<const bf16_t*>(v),                      \
-                         static_cast<const bf16_t*>(dout), lse, delta,       \
-                         static_cast<bf16_t*>(dk), static_cast<bf16_t*>(dv), \
-                         S, H, scale, causal, q_bs, q_hs, q_rs, o_bs, o_hs,  \
-                         o_rs);                                              \
-    else                                                                     \
     hipLaunchKernelGGL(flash_bwd_kv_kernel<DD>, kgrid, dim3(512), 0, stream, \
                        static_cast<const bf16_t*>(q),                        \
                        static_cast<const bf16_t*>(k),                        \

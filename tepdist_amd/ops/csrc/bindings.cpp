@@ -317,6 +317,10 @@ PYBIND11_MODULE(_tepdist_hip, m) {
                S(stream));
   });
 
+  m.def("tr16_frag_probe", [](uintptr_t out, int C, uintptr_t stream) {
+    tr16_frag_probe(reinterpret_cast<int*>(out), C, S(stream));
+  });
+
   m.def("adamw_mt", [](uintptr_t tabs, uintptr_t numel, uintptr_t wds,
                        uintptr_t ptypes, uintptr_t chunks, int nchunks,
                        int nt, float lr, float b1, float b2, float eps,

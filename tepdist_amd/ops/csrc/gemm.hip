@@ -13,11 +13,17 @@
 //    wgrad operands): each thread loads an 8(k) x 2(f) slab with eight 4B
 //    loads (f-coalesced across the wave), transposes it in registers with
 //    eight v_perm_b32, and writes two k-contiguous 16B rows. No scalar LDS
-//    traffic. (ds_read_b64_tr_b16 was measured — see debug.hip tr16_probe —
-//    to deliver only 16 distinct values per 16-lane group: each quad reads
-//    the (lane&3)-th bf16 of 4 rows based at the group's quad-LEADER
-//    addresses, so it cannot feed a 16x16 MFMA fragment; the register
-//    transpose path is the fast one.)
+//    traffic. (ds_read_b64_tr_b16 could form these fragments at read time
+//    from the natural [K][F] image instead: per 16-lane group, lane 4q+p
+//    supplies the 8B-aligned address of row q, columns 4p..4p+3 of a
+//    4-row x 16-column block and lane i receives column i of the four rows
+//    — two such reads make one 16x16x32 fragment, as tr_frag in lds_frag.h
+//    does for the flash kernels. The first probe here, debug.hip tr16_probe,
+//    addressed it as element lane&15 of row lane>>4; those unaligned
+//    addresses collapse to the quad leaders' 8B words, which is why it saw
+//    only 16 distinct values per group and this path took the register
+//    transpose. The GEMM has not been re-measured with the right
+//    addressing.)
 //
 // Replaces the reference's XLA-codegen GEMMs (all device code
 // in TePDist is XLA-generated PTX; here it is hand-written CDNA4).

@@ -154,6 +154,8 @@ void adamw_mt_bf16(const int64_t* tabs, const int64_t* numel,
 
 // --- diagnostics -----------------------------------------------------------
 void tr16_probe(float* out_pattern, float* out_uniform, hipStream_t stream);
+// out: int32 [2][C/16][64][8], see debug.hip
+void tr16_frag_probe(int* out, int C, hipStream_t stream);
 
 // --- Llama-family ops ------------------------------------------------------
 void rmsnorm_fwd_bf16(const void* x, const void* g, void* y, float* rstd,
