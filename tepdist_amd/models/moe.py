@@ -13,6 +13,7 @@ xla_sharding.replicate, moe_layers.py:296)."""
 
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
@@ -57,15 +58,49 @@ class _AllToAllVar(torch.autograd.Function):
         return dx, None, None, None
 
 
+ROUTE_MODES = ("fused", "composed", "auto")
+
+
+def _route_mode(route: Optional[str]) -> str:
+    """`route` or, when None, TEPDIST_MOE_ROUTE (default "auto")."""
+    if route is None:
+        route = os.environ.get("TEPDIST_MOE_ROUTE", "auto")
+    if route not in ROUTE_MODES:
+        raise ValueError(f"MoE route must be one of {ROUTE_MODES}, "
+                         f"got {route!r}")
+    return route
+
+
+def _use_fused(mode: str, x: torch.Tensor, E: int, k: int) -> bool:
+    """"fused" = ops.moe_route/moe_dispatch/moe_combine (the kernels of
+    ops/csrc/moe_route.hip on the GPU, the reference ops on CPU);
+    "composed" = the torch-op sequence. "auto" takes the fused path on the
+    GPU where the kernels' conditions hold (measured: docs/KERNELS.md "MoE
+    routing") and stays composed otherwise and on CPU."""
+    if mode == "auto":
+        return x.is_cuda and x.dtype == torch.bfloat16 and \
+            x.shape[-1] % 8 == 0 and 2 <= E <= 64 and k <= 4
+    return mode == "fused"
+
+
+def _gate_weights(gates: torch.Tensor, topi: torch.Tensor) -> torch.Tensor:
+    """Normalised fp32 weights [T, k] of the chosen experts (autograd to
+    gates)."""
+    w = gates.float().gather(1, topi.long())
+    return w / w.sum(-1, keepdim=True).clamp_min(1e-9)
+
+
 class MoELayer(nn.Module):
     """Top-2 gated FFN experts with capacity dropping and EP all-to-all."""
 
     def __init__(self, d: int, num_experts: int, top_k: int = 2,
                  capacity_factor: float = 1.25,
                  env: Optional[ParallelEnv] = None, ep_group=None,
-                 ep_size: int = 1, ep_rank: int = 0, dtype=torch.bfloat16):
+                 ep_size: int = 1, ep_rank: int = 0, dtype=torch.bfloat16,
+                 route: Optional[str] = None):
         super().__init__()
         assert num_experts % ep_size == 0
+        self.route = _route_mode(route)
         self.d = d
         self.E = num_experts
         self.k = top_k
@@ -97,21 +132,32 @@ class MoELayer(nn.Module):
         xt = x.reshape(T, d)
         logits = ops.linear(xt, self.w_gate)             # [T, E]
         gates = ops.softmax(logits.unsqueeze(0)).squeeze(0)
-        topv, topi = torch.topk(gates.float(), self.k, dim=-1)  # [T, k]
-        denom = topv.sum(-1, keepdim=True).clamp_min(1e-9)
-        topv = topv / denom
+        C = max(int(self.cf * T * self.k / self.E), 4)   # static capacity
+        fused = _use_fused(self.route, xt, self.E, self.k)
+        if fused:
+            route = ops.moe_route(gates, self.k, C)
+            topv = _gate_weights(gates, route.topi)          # [T, k] fp32
+            f = route.counts.float() / (T * self.k)
+        else:
+            topv, topi = torch.topk(gates.float(), self.k, dim=-1)  # [T, k]
+            denom = topv.sum(-1, keepdim=True).clamp_min(1e-9)
+            topv = topv / denom
+            with torch.no_grad():
+                f = torch.zeros(self.E, device=x.device)
+                f.scatter_add_(0, topi.reshape(-1),
+                               torch.ones_like(topi.reshape(-1),
+                                               dtype=torch.float32))
+                f = f / (T * self.k)
 
         # load-balancing aux loss (GShard): E * sum_e f_e * P_e
-        with torch.no_grad():
-            f = torch.zeros(self.E, device=x.device)
-            f.scatter_add_(0, topi.reshape(-1),
-                           torch.ones_like(topi.reshape(-1),
-                                           dtype=torch.float32))
-            f = f / (T * self.k)
         P = gates.float().mean(0)
         self.aux_loss = self.E * (f * P).sum()
 
-        C = max(int(self.cf * T * self.k / self.E), 4)   # static capacity
+        if fused:
+            D = ops.moe_dispatch(xt, route)              # [E*C, d]
+            back = self._experts(D, C, d)
+            out = ops.moe_combine(back, topv, route)
+            return out.reshape(B, S, d)
 
         flat_e = topi.reshape(-1)                        # [T*k]
         flat_w = topv.reshape(-1)
@@ -134,6 +180,19 @@ class MoELayer(nn.Module):
         D = torch.zeros(self.E * C, d, dtype=xt.dtype, device=x.device)
         D = D.index_put((slot_safe,), contrib, accumulate=True)
 
+        back = self._experts(D, C, d)
+
+        # combine: gather each (token, slot)'s expert output, weight, sum
+        gathered = back[slot_safe] * \
+            (flat_w * keep.to(flat_w.dtype)).unsqueeze(-1).to(back.dtype)
+        out = torch.zeros_like(xt).index_add(0, flat_t,
+                                             gathered.to(xt.dtype))
+        return out.reshape(B, S, d)
+
+    def _experts(self, D: torch.Tensor, C: int, d: int) -> torch.Tensor:
+        """D [E*C, d] dispatched slots -> expert outputs [E*C, d] in the
+        same slot order (EP all-to-all out, local experts, all-to-all
+        back)."""
         if self.ep_size > 1:
             from tepdist_amd.parallel.mappings import all_to_all
             Dx = all_to_all(D, self.ep_group)            # equal splits
@@ -158,12 +217,7 @@ class MoELayer(nn.Module):
                 self.ep_group)
         else:
             back = Y.reshape(self.E * C, d)
-
-        # combine: gather each (token, slot)'s expert output, weight, sum
-        gathered = back[slot_safe] *             (flat_w * keep.to(flat_w.dtype)).unsqueeze(-1).to(back.dtype)
-        out = torch.zeros_like(xt).index_add(0, flat_t,
-                                             gathered.to(xt.dtype))
-        return out.reshape(B, S, d)
+        return back
 
 
 class GPTMoEBlock(nn.Module):
@@ -283,7 +337,7 @@ class GPTMoE(nn.Module):
 # -- functional static-capacity dispatch/combine (the IR ops' semantics) ----
 
 def static_dispatch(x: torch.Tensor, gates: torch.Tensor, k: int,
-                    capacity: int):
+                    capacity: int, route: Optional[str] = None):
     """GShard dispatch with BLOCKED capacity: x [T, d], gates [T, E] ->
     D [E, C, d]. Deterministic in (x, gates); autograd flows through the
     gather/scatter and the combine weights. Shared by MoELayer and the
@@ -292,6 +346,14 @@ def static_dispatch(x: torch.Tensor, gates: torch.Tensor, k: int,
     grouped tensor — what makes expert parallelism a planner reshard)."""
     T, d = x.shape
     E = gates.shape[1]
+    if _use_fused(_route_mode(route), x, E, k):
+        rt = ops.moe_route(gates, k, capacity)
+        D = ops.moe_dispatch(x, rt)
+        flat_t = torch.arange(T, device=x.device).repeat_interleave(k)
+        slot = rt.slot.reshape(-1).long()
+        return D.reshape(E, capacity, d), (
+            flat_t, slot.clamp_min(0), slot >= 0,
+            _gate_weights(gates, rt.topi).reshape(-1))
     topv, topi = torch.topk(gates.float(), k, dim=-1)
     topv = topv / topv.sum(-1, keepdim=True).clamp_min(1e-9)
     flat_e = topi.reshape(-1)
@@ -314,11 +376,18 @@ def static_dispatch(x: torch.Tensor, gates: torch.Tensor, k: int,
 
 
 def static_combine(y: torch.Tensor, x: torch.Tensor, gates: torch.Tensor,
-                   k: int):
+                   k: int, route: Optional[str] = None):
     """Inverse of static_dispatch: y [E, C, d] expert outputs -> [T, d]
-    (recomputes the deterministic slot map from gates)."""
+    (recomputes the deterministic slot map from gates; the fused path
+    runs route + combine only, D is not rebuilt)."""
     E, C, d = y.shape
-    _, (flat_t, slot_safe, keep, flat_w) = static_dispatch(x, gates, k, C)
+    mode = _route_mode(route)
+    if _use_fused(mode, x, E, k):
+        rt = ops.moe_route(gates, k, C)
+        return ops.moe_combine(y.reshape(E * C, d),
+                               _gate_weights(gates, rt.topi), rt)
+    _, (flat_t, slot_safe, keep, flat_w) = static_dispatch(x, gates, k, C,
+                                                           "composed")
     back = y.reshape(E * C, d)
     gathered = back[slot_safe] * \
         (flat_w * keep.to(flat_w.dtype)).unsqueeze(-1).to(back.dtype)

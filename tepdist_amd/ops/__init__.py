@@ -9,6 +9,10 @@ from tepdist_amd.ops.interface import (  # noqa: F401
     attention,
     attention_qkv,
     decode_attention,
+    MoERoute,
+    moe_route,
+    moe_dispatch,
+    moe_combine,
     embedding,
     cross_entropy,
     dropout,

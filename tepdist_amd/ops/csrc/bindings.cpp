@@ -161,6 +161,51 @@ PYBIND11_MODULE(_tepdist_hip, m) {
     check_launch();
   });
 
+  m.def("moe_route_ws_ints", &moe_route_ws_ints);
+
+  m.def("moe_route", [](uintptr_t gates, bool gates_fp32, uintptr_t topi,
+                        uintptr_t slot, uintptr_t src, uintptr_t counts,
+                        uintptr_t ws, int T, int E, int k, int C,
+                        uintptr_t stream) {
+    moe_route(reinterpret_cast<const void*>(gates), gates_fp32,
+              reinterpret_cast<int*>(topi), reinterpret_cast<int*>(slot),
+              reinterpret_cast<int*>(src), reinterpret_cast<int*>(counts),
+              reinterpret_cast<int*>(ws), T, E, k, C, S(stream));
+    check_launch();
+  });
+
+  m.def("moe_gather_rows", [](uintptr_t in, uintptr_t src, uintptr_t w,
+                              uintptr_t out, int T, int k, int64_t EC, int d,
+                              uintptr_t stream) {
+    moe_gather_rows_bf16(reinterpret_cast<const void*>(in),
+                         reinterpret_cast<const int*>(src),
+                         reinterpret_cast<const float*>(w),
+                         reinterpret_cast<void*>(out), T, k, EC, d,
+                         S(stream));
+    check_launch();
+  });
+
+  m.def("moe_reduce_rows", [](uintptr_t in, uintptr_t slot, uintptr_t w,
+                              uintptr_t out, int T, int k, int64_t EC, int d,
+                              uintptr_t stream) {
+    moe_reduce_rows_bf16(reinterpret_cast<const void*>(in),
+                         reinterpret_cast<const int*>(slot),
+                         reinterpret_cast<const float*>(w),
+                         reinterpret_cast<void*>(out), T, k, EC, d,
+                         S(stream));
+    check_launch();
+  });
+
+  m.def("moe_combine_dw", [](uintptr_t y, uintptr_t dout, uintptr_t slot,
+                             uintptr_t dw, int T, int k, int64_t EC, int d,
+                             uintptr_t stream) {
+    moe_combine_dw_bf16(reinterpret_cast<const void*>(y),
+                        reinterpret_cast<const void*>(dout),
+                        reinterpret_cast<const int*>(slot),
+                        reinterpret_cast<float*>(dw), T, k, EC, d, S(stream));
+    check_launch();
+  });
+
   m.def("embedding_fwd",[](uintptr_t ids, uintptr_t table, uintptr_t out,
                             int64_t n_ids, int dim, uintptr_t stream) {
     embedding_fwd_bf16(reinterpret_cast<const int64_t*>(ids),

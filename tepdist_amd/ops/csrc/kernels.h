@@ -109,6 +109,35 @@ void decode_attention_bf16(const void* q, const void* k_new,
                            int64_t c_bs, int64_t c_hs, int64_t c_rs,
                            hipStream_t stream);
 
+// --- MoE routing / dispatch / combine (moe_route.hip) ----------------------
+// All maps are int32. gates [T,E] contiguous (bf16, or fp32 when
+// gates_fp32), 2 <= E <= 64, 1 <= k <= min(4,E), C >= 1, T*k < 2^31,
+// E*C < 2^31. Writes every element of topi [T,k] (k largest gates, ties to
+// the lower expert), slot [T,k] (e*C + pos in stable flat order, -1 when
+// pos >= C), src [E*C] (t*k + j of the entry in the slot, -1 when empty)
+// and counts [E] (selections per expert before dropping). ws: int32
+// [moe_route_ws_ints(T, E)], overwritten. Three launches, no atomics.
+int64_t moe_route_ws_ints(int T, int E);
+void moe_route(const void* gates, bool gates_fp32, int* topi, int* slot,
+               int* src, int* counts, int* ws, int T, int E, int k, int C,
+               hipStream_t stream);
+// out [EC,d] := (w[src[s]] *) in[src[s] / k, :] for a filled slot, zeros for
+// an empty one; in [T,d]. w null = unweighted (dispatch fwd); w fp32 [T*k]
+// = combine bwd dy. bf16 rows, d % 8 == 0, 16-byte aligned bases,
+// EC * d / 8 < 2^31.
+void moe_gather_rows_bf16(const void* in, const int* src, const float* w,
+                          void* out, int T, int k, int64_t EC, int d,
+                          hipStream_t stream);
+// out [T,d] := sum over kept j of (w[t,j] *) in[slot[t,j], :]; in [EC,d];
+// fp32 accumulation, one rounding. w null = dispatch bwd, else combine fwd.
+void moe_reduce_rows_bf16(const void* in, const int* slot, const float* w,
+                          void* out, int T, int k, int64_t EC, int d,
+                          hipStream_t stream);
+// dw [T,k] fp32 := dot(y[slot[t,j], :], dout[t, :]), exactly 0 when dropped.
+void moe_combine_dw_bf16(const void* y, const void* dout, const int* slot,
+                         float* dw, int T, int k, int64_t EC, int d,
+                         hipStream_t stream);
+
 // --- Embedding -------------------------------------------------------------
 void embedding_fwd_bf16(const int64_t* ids, const void* table, void* out,
                         int64_t n_ids, int dim, hipStream_t stream);

@@ -1002,3 +1002,131 @@ def swiglu_bwd(dy: torch.Tensor, a: torch.Tensor, b: torch.Tensor):
     ext.swiglu_bwd(dy.data_ptr(), a.data_ptr(), b.data_ptr(), da.data_ptr(),
                    db.data_ptr(), a.numel(), _stream())
     return da, db
+
+
+# --------------------------------------------------------------------------
+# MoE routing / dispatch / combine (csrc/moe_route.hip)
+# --------------------------------------------------------------------------
+
+_I32 = torch.int32
+
+
+def _moe_rows(name: str, t: torch.Tensor, what: str):
+    if t.dim() != 2 or t.dtype != BF16 or not t.is_cuda:
+        raise ValueError(f"{name}: {what} must be a 2-D bf16 device tensor")
+    if t.shape[1] < 8 or t.shape[1] % 8:
+        raise ValueError(f"{name}: row width {t.shape[1]} is not a positive "
+                         "multiple of 8")
+    if not t.is_contiguous() or t.data_ptr() % 16:
+        raise ValueError(f"{name}: {what} must be contiguous and 16-byte "
+                         "aligned")
+
+
+def _moe_map(name: str, t: torch.Tensor, shape, what: str,
+             dtype=_I32):
+    if t.dtype != dtype or not t.is_cuda or tuple(t.shape) != tuple(shape) \
+            or not t.is_contiguous():
+        raise ValueError(f"{name}: {what} must be a contiguous {dtype} "
+                         f"device tensor of shape {tuple(shape)}, got "
+                         f"{t.dtype} {tuple(t.shape)}")
+
+
+def _moe_k(name: str, T: int, k: int, EC: int):
+    if not 1 <= k <= 4 or T < 1 or T * k >= 2 ** 31 or \
+            not 1 <= EC < 2 ** 31:
+        raise ValueError(f"{name}: need 1 <= k <= 4, T*k < 2^31 and "
+                         f"1 <= E*C < 2^31 (T={T}, k={k}, E*C={EC})")
+
+
+def moe_route(gates: torch.Tensor, k: int, capacity: int):
+    """Same contract as reference.moe_route; every output element is
+    written by the kernels (three launches, no atomics, no host sync)."""
+    if gates.dim() != 2 or not gates.is_cuda:
+        raise ValueError("moe_route: gates must be a [T, E] device tensor")
+    if gates.dtype not in (BF16, torch.float32):
+        raise ValueError("moe_route: gates must be bf16 or fp32")
+    if not gates.is_contiguous():
+        raise ValueError("moe_route: gates must be contiguous")
+    T, E = gates.shape
+    k, C = int(k), int(capacity)
+    if not 2 <= E <= 64:
+        raise ValueError(f"moe_route: E={E} not in [2, 64]")
+    if not 1 <= k <= min(4, E):
+        raise ValueError(f"moe_route: k={k} not in [1, min(4, E)]")
+    if C < 1:
+        raise ValueError("moe_route: capacity must be >= 1")
+    _moe_k("moe_route", T, k, E * C)
+    dev = gates.device
+    topi = torch.empty(T, k, dtype=_I32, device=dev)
+    slot = torch.empty(T, k, dtype=_I32, device=dev)
+    src = torch.empty(E * C, dtype=_I32, device=dev)
+    counts = torch.empty(E, dtype=_I32, device=dev)
+    ws = torch.empty(ext.moe_route_ws_ints(T, E), dtype=_I32, device=dev)
+    ext.moe_route(gates.data_ptr(), gates.dtype == torch.float32,
+                  topi.data_ptr(), slot.data_ptr(), src.data_ptr(),
+                  counts.data_ptr(), ws.data_ptr(), T, E, k, C, _stream())
+    return topi, slot, src, counts
+
+
+def moe_dispatch_fwd(x: torch.Tensor, src: torch.Tensor, k: int):
+    _moe_rows("moe_dispatch", x, "x")
+    T, d = x.shape
+    EC = src.numel()
+    _moe_k("moe_dispatch", T, k, EC)
+    _moe_map("moe_dispatch", src, (EC,), "src")
+    D = torch.empty(EC, d, dtype=BF16, device=x.device)
+    ext.moe_gather_rows(x.data_ptr(), src.data_ptr(), 0, D.data_ptr(), T, k,
+                        EC, d, _stream())
+    return D
+
+
+def moe_dispatch_bwd(dD: torch.Tensor, slot: torch.Tensor):
+    _moe_rows("moe_dispatch backward", dD, "dD")
+    EC, d = dD.shape
+    if slot.dim() != 2:
+        raise ValueError("moe_dispatch backward: slot must be [T, k]")
+    T, k = slot.shape
+    _moe_k("moe_dispatch backward", T, k, EC)
+    _moe_map("moe_dispatch backward", slot, (T, k), "slot")
+    dx = torch.empty(T, d, dtype=BF16, device=dD.device)
+    ext.moe_reduce_rows(dD.data_ptr(), slot.data_ptr(), 0, dx.data_ptr(), T,
+                        k, EC, d, _stream())
+    return dx
+
+
+def moe_combine_fwd(y: torch.Tensor, w: torch.Tensor, slot: torch.Tensor):
+    _moe_rows("moe_combine", y, "y")
+    EC, d = y.shape
+    if slot.dim() != 2:
+        raise ValueError("moe_combine: slot must be [T, k]")
+    T, k = slot.shape
+    _moe_k("moe_combine", T, k, EC)
+    _moe_map("moe_combine", slot, (T, k), "slot")
+    _moe_map("moe_combine", w, (T, k), "weights", torch.float32)
+    out = torch.empty(T, d, dtype=BF16, device=y.device)
+    ext.moe_reduce_rows(y.data_ptr(), slot.data_ptr(), w.data_ptr(),
+                        out.data_ptr(), T, k, EC, d, _stream())
+    return out
+
+
+def moe_combine_bwd(dout: torch.Tensor, y: torch.Tensor, w: torch.Tensor,
+                    slot: torch.Tensor, src: torch.Tensor):
+    _moe_rows("moe_combine backward", y, "y")
+    _moe_rows("moe_combine backward", dout, "dout")
+    EC, d = y.shape
+    if slot.dim() != 2:
+        raise ValueError("moe_combine backward: slot must be [T, k]")
+    T, k = slot.shape
+    _moe_k("moe_combine backward", T, k, EC)
+    if tuple(dout.shape) != (T, d):
+        raise ValueError("moe_combine backward: dout must be [T, d]")
+    _moe_map("moe_combine backward", slot, (T, k), "slot")
+    _moe_map("moe_combine backward", src, (EC,), "src")
+    _moe_map("moe_combine backward", w, (T, k), "weights", torch.float32)
+    dy = torch.empty(EC, d, dtype=BF16, device=y.device)
+    dw = torch.empty(T, k, dtype=torch.float32, device=y.device)
+    ext.moe_gather_rows(dout.data_ptr(), src.data_ptr(), w.data_ptr(),
+                        dy.data_ptr(), T, k, EC, d, _stream())
+    ext.moe_combine_dw(y.data_ptr(), dout.data_ptr(), slot.data_ptr(),
+                       dw.data_ptr(), T, k, EC, d, _stream())
+    return dy, dw

@@ -10,7 +10,7 @@ Every op the planner shards goes through here. Dispatch:
 
 from __future__ import annotations
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -288,6 +288,71 @@ def decode_attention(q, k_cache, v_cache, positions, k_new=None, v_new=None,
                                     v_new, scale)
     return be.decode_attention(q, k_cache, v_cache, positions, k_new, v_new,
                                scale, splits)
+
+
+# --------------------------------------------------------------------------
+# MoE routing / dispatch / combine
+# --------------------------------------------------------------------------
+
+
+class MoERoute(NamedTuple):
+    """Slot maps of one routing decision (all int32): topi [T, k] chosen
+    experts, slot [T, k] = e*C + pos or -1 (dropped), src [E*C] = t*k + j
+    or -1 (empty), counts [E] selections per expert before dropping."""
+    topi: torch.Tensor
+    slot: torch.Tensor
+    src: torch.Tensor
+    counts: torch.Tensor
+
+
+def moe_route(gates, k: int, capacity: int) -> MoERoute:
+    """Top-k routing with static capacity for gates [T, E] (no autograd).
+    Ties go to the lower expert index; positions within an expert follow
+    the flat (t, j) order. See reference.moe_route for the exact rules."""
+    return MoERoute(*_backend(gates).moe_route(gates.detach(), k, capacity))
+
+
+class MoEDispatchFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, src, slot):
+        ctx.save_for_backward(slot)
+        return _backend(x).moe_dispatch_fwd(x.contiguous(), src,
+                                            slot.shape[1])
+
+    @staticmethod
+    def backward(ctx, dD):
+        (slot,) = ctx.saved_tensors
+        return _backend(dD).moe_dispatch_bwd(dD.contiguous(), slot), \
+            None, None
+
+
+def moe_dispatch(x, route: MoERoute):
+    """x [T, d] -> D [E*C, d]: slot s holds the token route.src[s] // k, an
+    empty slot holds zeros. Autograd to x."""
+    return MoEDispatchFn.apply(x, route.src, route.slot)
+
+
+class MoECombineFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, w, slot, src):
+        y = y.contiguous()
+        w = w.contiguous()
+        ctx.save_for_backward(y, w, slot, src)
+        return _backend(y).moe_combine_fwd(y, w, slot)
+
+    @staticmethod
+    def backward(ctx, dout):
+        y, w, slot, src = ctx.saved_tensors
+        dy, dw = _backend(dout).moe_combine_bwd(dout.contiguous(), y, w,
+                                                slot, src)
+        return dy, dw, None, None
+
+
+def moe_combine(y, weights, route: MoERoute):
+    """y [E*C, d], weights [T, k] fp32 -> out [T, d] = sum over kept j of
+    weights[t, j] * y[route.slot[t, j]]. Autograd to y and weights; what a
+    never-filled slot of y holds does not reach the output."""
+    return MoECombineFn.apply(y, weights, route.slot, route.src)
 
 
 # --------------------------------------------------------------------------

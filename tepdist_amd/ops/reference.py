@@ -384,3 +384,83 @@ def swiglu_bwd(dy: torch.Tensor, a: torch.Tensor, b: torch.Tensor):
     da = dyf * bf * (sig + silu * (1.0 - sig))
     db = dyf * silu
     return da.to(a.dtype), db.to(b.dtype)
+
+
+# --------------------------------------------------------------------------
+# MoE routing / dispatch / combine (any dtype, any device; the rules the
+# fused kernels in csrc/moe_route.hip implement)
+# --------------------------------------------------------------------------
+
+def _acc_dtype(t: torch.Tensor):
+    return torch.promote_types(t.dtype, torch.float32)
+
+
+def moe_route(gates: torch.Tensor, k: int, capacity: int):
+    """gates [T, E] -> (topi [T, k], slot [T, k], src [E*C], counts [E]),
+    all int32. topi[t, j] is the expert with the j-th largest gate, ties to
+    the lower expert index (stable descending sort). slot = e*C + pos with
+    pos the number of earlier flat entries (t*k + j order) that chose e, or
+    -1 where pos >= C. src is the inverse map (-1 for an empty slot).
+    counts[e] is the number of selections of e before capacity dropping."""
+    T, E = gates.shape
+    C = int(capacity)
+    g = gates if gates.dtype in (torch.float32, torch.float64) \
+        else gates.float()
+    topi = torch.sort(g, dim=-1, descending=True,
+                      stable=True).indices[:, :k]
+    flat_e = topi.reshape(-1)
+    n = flat_e.numel()
+    order = torch.argsort(flat_e, stable=True)
+    counts = torch.bincount(flat_e, minlength=E)
+    offs = torch.cumsum(counts, 0) - counts
+    r = torch.arange(n, device=gates.device)
+    pos = torch.empty_like(r)
+    pos[order] = r - offs[flat_e[order]]
+    keep = pos < C
+    slot = torch.where(keep, flat_e * C + pos, torch.full_like(pos, -1))
+    src = torch.full((E * C,), -1, dtype=torch.long, device=gates.device)
+    src[slot[keep]] = r[keep]
+    i32 = torch.int32
+    return (topi.to(i32).contiguous(), slot.reshape(T, k).to(i32),
+            src.to(i32), counts.to(i32))
+
+
+def moe_dispatch_fwd(x: torch.Tensor, src: torch.Tensor, k: int):
+    """D[s] = x[src[s] // k] for a filled slot, zeros for an empty one."""
+    s = src.long()
+    rows = x[s.clamp_min(0) // k]
+    return torch.where((s >= 0).unsqueeze(-1), rows, torch.zeros_like(rows))
+
+
+def moe_dispatch_bwd(dD: torch.Tensor, slot: torch.Tensor):
+    """dx[t] = sum over kept j of dD[slot[t, j]] (fp32 sum, one rounding)."""
+    s = slot.long()
+    rows = dD[s.clamp_min(0)].to(_acc_dtype(dD))             # [T, k, d]
+    rows = torch.where((s >= 0).unsqueeze(-1), rows, torch.zeros_like(rows))
+    return rows.sum(1).to(dD.dtype)
+
+
+def moe_combine_fwd(y: torch.Tensor, w: torch.Tensor, slot: torch.Tensor):
+    """out[t] = sum over kept j of w[t, j] * y[slot[t, j]]; dropped entries
+    are selected away, so a never-filled slot of y has no influence."""
+    s = slot.long()
+    acc = _acc_dtype(y)
+    rows = y[s.clamp_min(0)].to(acc) * w.to(acc).unsqueeze(-1)
+    rows = torch.where((s >= 0).unsqueeze(-1), rows, torch.zeros_like(rows))
+    return rows.sum(1).to(y.dtype)
+
+
+def moe_combine_bwd(dout: torch.Tensor, y: torch.Tensor, w: torch.Tensor,
+                    slot: torch.Tensor, src: torch.Tensor):
+    """dy[s] = w[src[s]] * dout[src[s] // k] (zeros for an empty slot);
+    dw[t, j] = dot(y[slot[t, j]], dout[t]) in fp32 (0 where dropped)."""
+    k = slot.shape[1]
+    acc = _acc_dtype(y)
+    s = src.long()
+    sc = s.clamp_min(0)
+    dy = w.reshape(-1)[sc].to(acc).unsqueeze(-1) * dout[sc // k].to(acc)
+    dy = torch.where((s >= 0).unsqueeze(-1), dy, torch.zeros_like(dy))
+    sl = slot.long()
+    dw = (y[sl.clamp_min(0)].to(acc) * dout.to(acc).unsqueeze(1)).sum(-1)
+    dw = torch.where(sl >= 0, dw, torch.zeros_like(dw))
+    return dy.to(y.dtype), dw.to(w.dtype)
