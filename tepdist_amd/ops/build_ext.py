@@ -57,6 +57,8 @@ def _needs_build() -> bool:
     so_mtime = OUT_SO.stat().st_mtime
     deps = [CSRC / s for s in SOURCES] + [CSRC / "common.h", CSRC / "kernels.h",
                                           CSRC / "lds_frag.h",
+                                          CSRC / "gemm_plan.h",
+                                          CSRC / "gemm_tile.h",
                                           Path(__file__)]
     return any(d.stat().st_mtime > so_mtime for d in deps)
 

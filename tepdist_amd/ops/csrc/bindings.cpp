@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "gemm_plan.h"
 #include "kernels.h"
 
 namespace py = pybind11;
@@ -27,21 +28,25 @@ PYBIND11_MODULE(_tepdist_hip, m) {
   m.def("gemm", [](uintptr_t A, uintptr_t B, uintptr_t C, uintptr_t Cpre,
                    uintptr_t bias, int M, int N, int K, int lda, int ldb,
                    int ldc, int64_t sa, int64_t sb, int64_t sc, int batch,
-                   bool a_kc, bool b_kc, int epi, int split_k,
+                   bool a_kc, bool b_kc, int epi, uintptr_t splitk_ws,
                    uintptr_t stream) {
     gemm_bf16(reinterpret_cast<void*>(A), reinterpret_cast<void*>(B),
               reinterpret_cast<void*>(C), reinterpret_cast<void*>(Cpre),
               reinterpret_cast<void*>(bias), M, N, K, lda, ldb, ldc, sa, sb,
-              sc, batch, a_kc, b_kc, epi, split_k, S(stream));
+              sc, batch, a_kc, b_kc, epi, reinterpret_cast<float*>(splitk_ws),
+              S(stream));
     check_launch();
   });
 
-  m.def("splitk_reduce", [](uintptr_t parts, uintptr_t out, int nparts,
-                            int64_t mn, uintptr_t stream) {
-    splitk_reduce(reinterpret_cast<const float*>(parts),
-                  reinterpret_cast<void*>(out), nparts, mn, S(stream));
-    check_launch();
-  });
+  // (kernel, split_k, k_chunk, why_not) — host-only, needs no GPU
+  m.def("gemm_plan", [](int M, int N, int K, int lda, int ldb, bool a_kc,
+                        bool b_kc, int epi, int batch) {
+    const GemmPlan p = gemm_plan(M, N, K, lda, ldb, a_kc, b_kc, epi, batch);
+    return py::make_tuple(p.kernel, p.split_k, p.k_chunk,
+                          p.why_not ? p.why_not : "");
+  }, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("lda"),
+     py::arg("ldb"), py::arg("a_kc") = true, py::arg("b_kc") = true,
+     py::arg("epi") = 0, py::arg("batch") = 1);
 
   m.def("transpose", [](uintptr_t in, uintptr_t out, int R, int C,
                         int64_t si, int64_t so, int batch,

@@ -33,29 +33,19 @@
 #include <string>
 
 #include "common.h"
+#include "gemm_tile.h"
 #include "kernels.h"
 
 namespace tepdist {
 
 namespace {
 
-constexpr int BM = 128, BN = 128, BK = 64;
+constexpr int BM = plan::T128, BN = plan::T128, BK = plan::BK;
 constexpr int SLOT = BM * BK;  // elements per operand slot
 constexpr int NTHREADS = 256;
 
-// LDS addressing: unpadded 128B rows + an XOR swizzle of the 16B column
-// slot by x(row) = bit-reversed (row>>1)&7. The bit reversal puts the
-// fragment-read service groups' row bit (row bit 1 under quad-strided
-// 16-lane grouping, row bits 1..3 under contiguous grouping) into slot
-// bits that the reads' own column spread does not already cover, making
-// ds_read_b128 column reads conflict-free; writes stay <=2-way.
-DEV_INLINE int lds_off(int row, int col_e) {
-  const int r1 = row >> 1;
-  const int x = ((r1 & 1) << 2) | (r1 & 2) | ((r1 >> 2) & 1);
-  return row * BK + (col_e ^ (x << 3));
-}
-
-enum { EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_GELU = 2, EPI_GELU = 3 };
+// LDS image: unpadded 128B rows, 16B column slots swizzled (lds_frag.h).
+DEV_INLINE int lds_off(int row, int col_e) { return loff<BK>(row, col_e); }
 
 // --- staging loads ---------------------------------------------------------
 
@@ -112,13 +102,8 @@ DEV_INLINE void stage_ko_load(const bf16_t* __restrict__ src, int F, int K,
 }
 
 // KC operand via global_load_lds (direct HBM->LDS DMA, 16B per lane; the
-// guide's step-3 lever). The glds destination is wave-uniform base + lane*16B
-// (lane-linear), so the XOR swizzle moves to the per-lane SOURCE address
-// (rule 21): LDS element (row, c) receives global k = c ^ (x(row)<<3).
+// guide's step-3 lever), swizzle on the source address (gemm_tile.h).
 // Only for fully-interior tiles (no bounds handling in the DMA).
-typedef __attribute__((address_space(1))) const void* glds_src_t;
-typedef __attribute__((address_space(3))) void* glds_dst_t;
-
 DEV_INLINE void stage_kc_glds(const bf16_t* __restrict__ src, int ld, int f0,
                               int k0, bf16_t* dst) {
   const int wave = threadIdx.x >> 6;
@@ -128,9 +113,7 @@ DEV_INLINE void stage_kc_glds(const bf16_t* __restrict__ src, int ld, int f0,
     const int idx = threadIdx.x + u * NTHREADS;
     const int row = idx >> 3;                 // dest row (lane-linear)
     const int c = (idx & 7) * 8;              // dest column (elements)
-    const int r1 = row >> 1;
-    const int x = ((r1 & 1) << 2) | (r1 & 2) | ((r1 >> 2) & 1);
-    const int ksrc = k0 + (c ^ (x << 3));     // inverse swizzle on the source
+    const int ksrc = k0 + (c ^ (SWZ8(row) << 3));  // inverse swizzle
     const bf16_t* g = src + (int64_t)(f0 + row) * ld + ksrc;
     bf16_t* l = dst + (8 * wave + 32 * u) * BK;  // wave-uniform base
     __builtin_amdgcn_global_load_lds((glds_src_t)g, (glds_dst_t)l, 16,
@@ -207,14 +190,8 @@ void gemm_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B,
     if (EPI >= 2) Cpre += blockIdx.z * strideC;
   }
 
-  // XCD-aware bijective block swizzle (guide T1): the dispatcher places
-  // block b on XCD b%8; remap so each XCD gets a CONTIGUOUS run of tiles
-  // (consecutive n-tiles share the A panel -> L2 hits stay on one XCD).
   const int nbx = (N + BN - 1) / BN;
-  const int nwg = gridDim.x;
-  const int q = nwg >> 3, r = nwg & 7;
-  const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-  const int swz = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+  const int swz = xcd_remap(blockIdx.x, gridDim.x);
   const int m0 = (swz / nbx) * BM, n0 = (swz % nbx) * BN;
 
   __shared__ bf16_t smem[2][2][SLOT];  // [buf][A=0/B=1]
@@ -364,78 +341,73 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ parts,
   }
 }
 
-}  // namespace
-
-void splitk_reduce(const float* parts, void* out, int nparts, int64_t mn,
+void splitk_reduce(const float* parts, bf16_t* out, int nparts, int64_t mn,
                    hipStream_t stream) {
   const int blocks = (int)std::min<int64_t>(
       (mn / 4 + NTHREADS - 1) / NTHREADS, 2048);
   hipLaunchKernelGGL(splitk_reduce_kernel, dim3(std::max(blocks, 1)),
-                     dim3(NTHREADS), 0, stream, parts,
-                     static_cast<bf16_t*>(out), nparts, mn);
+                     dim3(NTHREADS), 0, stream, parts, out, nparts, mn);
 }
+
+}  // namespace
 
 void gemm_bf16(const void* A, const void* B, void* C, void* c_pre,
                const void* bias, int M, int N, int K, int lda, int ldb,
                int ldc, int64_t stride_a, int64_t stride_b, int64_t stride_c,
-               int batch, bool a_kc, bool b_kc, int epi, int split_k,
+               int batch, bool a_kc, bool b_kc, int epi, float* splitk_ws,
                hipStream_t stream) {
-  const int nbx = (N + BN - 1) / BN, nby = (M + BM - 1) / BM;
-  dim3 block(NTHREADS);
-  const bf16_t* a = static_cast<const bf16_t*>(A);
-  const bf16_t* b = static_cast<const bf16_t*>(B);
-  bf16_t* cp = static_cast<bf16_t*>(c_pre);
-  const bf16_t* bi = static_cast<const bf16_t*>(bias);
+  const GemmPlan p = gemm_plan(M, N, K, lda, ldb, a_kc, b_kc, epi, batch);
+  if (p.kernel == 0)
+    throw std::runtime_error(std::string("gemm_bf16: ") + p.why_not);
 
-  if (split_k > 1) {
-    if (batch != 1 || epi != 0)
-      throw std::runtime_error("split_k requires batch=1, epi=0");
-    if (gemm256_supported(M, N, K, lda, ldb, a_kc, b_kc, epi, split_k)) {
-      gemm256_bf16(A, B, C, c_pre, bias, M, N, K, lda, ldb, ldc, stride_a,
-                   stride_b, stride_c, batch, epi, split_k, stream);
-      return;
+  // split-K: chunk z writes fp32 partials [M, N] at splitk_ws + z*M*N,
+  // reduced into C (contiguous) by a second launch
+  const bool split = p.split_k > 1;
+  const int64_t mn = (int64_t)M * N;
+  if (split && splitk_ws == nullptr)
+    throw std::runtime_error("gemm_bf16: split-K plan needs a workspace of " +
+                             std::to_string(p.split_k * mn) + " floats");
+  if (split && ldc != N)
+    throw std::runtime_error("gemm_bf16: split-K plan needs ldc == N");
+  void* out = C;
+  if (split) {
+    out = splitk_ws;
+    stride_c = mn;
+  }
+
+  if (p.kernel == plan::T256) {
+    gemm256_bf16(A, B, out, c_pre, bias, M, N, K, lda, ldb, ldc, stride_a,
+                 stride_b, stride_c, batch, epi, p.split_k, p.k_chunk, stream);
+  } else {
+    const int nbx = (N + BN - 1) / BN, nby = (M + BM - 1) / BM;
+    const dim3 grid(nbx * nby, 1, split ? p.split_k : batch), block(NTHREADS);
+    const bf16_t* a = static_cast<const bf16_t*>(A);
+    const bf16_t* b = static_cast<const bf16_t*>(B);
+    bf16_t* cp = static_cast<bf16_t*>(c_pre);
+    const bf16_t* bi = static_cast<const bf16_t*>(bias);
+#define GEMM_LAUNCH(AKC, BKC, E, F32)                                       \
+    hipLaunchKernelGGL((gemm_kernel<AKC, BKC, E, F32>), grid, block, 0,     \
+                       stream, a, b, out, cp, bi, M, N, K, lda, ldb, ldc,   \
+                       stride_a, stride_b, stride_c, p.k_chunk)
+#define GEMM_EPI(AKC, BKC)                                                  \
+    if (split) { GEMM_LAUNCH(AKC, BKC, 0, true); }                          \
+    else switch (epi) {  /* the plan admits epi 0..3 here */                \
+      case EPI_NONE: GEMM_LAUNCH(AKC, BKC, EPI_NONE, false); break;         \
+      case EPI_BIAS: GEMM_LAUNCH(AKC, BKC, EPI_BIAS, false); break;         \
+      case EPI_BIAS_GELU: GEMM_LAUNCH(AKC, BKC, EPI_BIAS_GELU, false); break; \
+      case EPI_GELU: GEMM_LAUNCH(AKC, BKC, EPI_GELU, false); break;         \
     }
-    const int k_chunk = ((K + split_k - 1) / split_k + BK - 1) / BK * BK;
-    dim3 gridk(nbx * nby, 1, split_k);
-#define GEMM_SK(AKC, BKC)                                                   \
-    hipLaunchKernelGGL((gemm_kernel<AKC, BKC, 0, true>), gridk, block, 0,   \
-                       stream, a, b, C, cp, bi, M, N, K, lda, ldb, ldc,     \
-                       stride_a, stride_b, stride_c, k_chunk)
-    if (a_kc && b_kc) { GEMM_SK(true, true); }
-    else if (a_kc && !b_kc) { GEMM_SK(true, false); }
-    else if (!a_kc && b_kc) { GEMM_SK(false, true); }
-    else { GEMM_SK(false, false); }
-#undef GEMM_SK
-    return;
-  }
-
-  if (gemm256_supported(M, N, K, lda, ldb, a_kc, b_kc, epi, 1)) {
-    gemm256_bf16(A, B, C, c_pre, bias, M, N, K, lda, ldb, ldc, stride_a,
-                 stride_b, stride_c, batch, epi, 1, stream);
-    return;
-  }
-
-  dim3 grid(nbx * nby, 1, batch);
-#define GEMM_LAUNCH(AKC, BKC, E)                                            \
-  hipLaunchKernelGGL((gemm_kernel<AKC, BKC, E>), grid, block, 0, stream, a, \
-                     b, C, cp, bi, M, N, K, lda, ldb, ldc, stride_a,        \
-                     stride_b, stride_c, 0)
-
-#define GEMM_EPI(AKC, BKC)                         \
-  switch (epi) {                                   \
-    case 0: GEMM_LAUNCH(AKC, BKC, 0); break;       \
-    case 1: GEMM_LAUNCH(AKC, BKC, 1); break;       \
-    case 2: GEMM_LAUNCH(AKC, BKC, 2); break;       \
-    case 3: GEMM_LAUNCH(AKC, BKC, 3); break;       \
-    default: throw std::runtime_error("bad epi");  \
-  }
-
-  if (a_kc && b_kc) { GEMM_EPI(true, true); }
-  else if (a_kc && !b_kc) { GEMM_EPI(true, false); }
-  else if (!a_kc && b_kc) { GEMM_EPI(false, true); }
-  else { GEMM_EPI(false, false); }
+    if (a_kc && b_kc) { GEMM_EPI(true, true); }
+    else if (a_kc && !b_kc) { GEMM_EPI(true, false); }
+    else if (!a_kc && b_kc) { GEMM_EPI(false, true); }
+    else { GEMM_EPI(false, false); }
 #undef GEMM_EPI
 #undef GEMM_LAUNCH
+  }
+  if (split) {
+    HIP_CHECK(hipGetLastError());
+    splitk_reduce(splitk_ws, static_cast<bf16_t*>(C), p.split_k, mn, stream);
+  }
 }
 
 }  // namespace tepdist

@@ -19,39 +19,25 @@
 // quarter-units (3 "half-tiles") in flight.
 //
 // Handles only the canonical case (both operands k-contiguous, M,N % 256
-// == 0, K % 64 == 0, 16B-aligned rows); gemm.hip covers the rest and
-// linear_bwd canonicalizes dgrad/wgrad into this case via transposes.
-
-#include <algorithm>
-#include <stdexcept>
+// == 0, K % 64 == 0, 16B-aligned rows, >= 2 K-tiles per chunk); gemm_plan.h
+// decides when that holds, gemm.hip covers the rest and linear_bwd
+// canonicalizes dgrad/wgrad into this case via transposes.
 
 #include "common.h"
+#include "gemm_tile.h"
 #include "kernels.h"
 
 namespace tepdist {
 
 namespace {
 
-constexpr int BM = 256, BN = 256, BK = 64;
+constexpr int BM = plan::T256, BN = plan::T256, BK = plan::BK;
 constexpr int NTH = 512;  // 8 waves
 constexpr int QROWS = 64;          // stage-unit rows
 constexpr int SLOT_E = QROWS * BK; // elements per slot (8 KiB)
 
-enum { EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_GELU = 2, EPI_GELU = 3,
-       // dgelu: C = (A@B) * gelu'(aux) — the Cpre pointer is the INPUT
-       // pre-activation saved by the forward (the fusion hipBLASLt has
-       // no algorithms for on gfx950, profiles/blaslt_epilogue_probe.md)
-       EPI_DGELU = 4 };
-
-typedef __attribute__((address_space(1))) const void* gsrc_t;
-typedef __attribute__((address_space(3))) void* gdst_t;
-
-// row swizzle within a [64][64] slot (see gemm.hip lds_off)
-DEV_INLINE int qoff(int row, int col_e) {
-  const int r1 = row >> 1;
-  const int x = ((r1 & 1) << 2) | (r1 & 2) | ((r1 >> 2) & 1);
-  return row * BK + (col_e ^ (x << 3));
-}
+// swizzled offset within a [64][64] slot / the [256][64] epilogue image
+DEV_INLINE int qoff(int row, int col_e) { return loff<BK>(row, col_e); }
 
 // stage one quarter unit: rows [f0, f0+64) x cols [k0, k0+64) of a
 // k-contiguous operand into slot `dst` (one glds dwordx4 per thread).
@@ -60,19 +46,15 @@ DEV_INLINE void stage_q(const bf16_t* __restrict__ src, int64_t ld, int f0,
   const int wave = threadIdx.x >> 6;
   const int row = threadIdx.x >> 3;          // 0..63 (lane-linear per wave)
   const int c = (threadIdx.x & 7) * 8;
-  const int r1 = row >> 1;
-  const int x = ((r1 & 1) << 2) | (r1 & 2) | ((r1 >> 2) & 1);
-  const int ksrc = k0 + (c ^ (x << 3));      // inverse swizzle on source
+  const int ksrc = k0 + (c ^ (SWZ8(row) << 3));  // inverse swizzle on source
   const bf16_t* g = src + (int64_t)(f0 + row) * ld + ksrc;
   bf16_t* l = dst + (8 * wave) * BK;         // wave-uniform base
-  __builtin_amdgcn_global_load_lds((gsrc_t)g, (gdst_t)l, 16, 0, 0);
+  __builtin_amdgcn_global_load_lds((glds_src_t)g, (glds_dst_t)l, 16, 0, 0);
 }
 
 // f32 image variant of the swizzle (16B slot = 4 floats)
 DEV_INLINE int qoff_f32(int row, int col_e) {
-  const int r1 = row >> 1;
-  const int x = ((r1 & 1) << 2) | (r1 & 2) | ((r1 >> 2) & 1);
-  return row * BK + (col_e ^ ((x << 2) & 63));
+  return row * BK + (col_e ^ (SWZ8(row) << 2));
 }
 
 DEV_INLINE bf16x8 fragq(const bf16_t* slot, int row, int col_e) {
@@ -105,13 +87,8 @@ void gemm256_kernel(const bf16_t* __restrict__ A,
     if (EPI >= 2) Cpre += blockIdx.z * strideC;
   }
 
-  // XCD-aware bijective swizzle (guide T1)
   const int nbx = N / BN;
-  const int nwg = gridDim.x;
-  const int qd = nwg >> 3, r = nwg & 7;
-  const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-  const int swz = (xcd < r ? xcd * (qd + 1) : r * (qd + 1) + (xcd - r) * qd)
-                  + idx;
+  const int swz = xcd_remap(blockIdx.x, gridDim.x);
   const int m0 = (swz / nbx) * BM, n0 = (swz % nbx) * BN;
 
   __shared__ bf16_t smem[16 * SLOT_E];  // A slots 0..7, B slots 8..15
@@ -317,50 +294,30 @@ void gemm256_kernel(const bf16_t* __restrict__ A,
 
 }  // namespace
 
-bool gemm256_supported(int M, int N, int K, int lda, int ldb, bool a_kc,
-                       bool b_kc, int epi, int split_k) {
-  if (!(a_kc && b_kc && M % BM == 0 && N % BN == 0 && K % BK == 0 &&
-        (lda & 7) == 0 && (ldb & 7) == 0))
-    return false;
-  if (split_k <= 1) return K >= 2 * BK;
-  const int chunk = (K / split_k + BK - 1) / BK * BK;
-  // every chunk must be >= 2 K-tiles (the pipeline's minimum) and the
-  // chunk count must be exactly split_k (rounding can otherwise leave
-  // trailing chunks with no K range, whose prologue would read past K)
-  return epi == 0 && chunk >= 2 * BK && K % chunk != BK &&
-         (K + chunk - 1) / chunk == split_k;
-}
-
+// Launches what gemm_plan() planned for the 256 kernel: split_k > 1 writes
+// fp32 partials (C is then the workspace), chunk z at C + z*stride_c.
 void gemm256_bf16(const void* A, const void* B, void* C, void* c_pre,
                   const void* bias, int M, int N, int K, int lda, int ldb,
                   int ldc, int64_t stride_a, int64_t stride_b,
                   int64_t stride_c, int batch, int epi, int split_k,
-                  hipStream_t stream) {
-  dim3 block(NTH);
+                  int k_chunk, hipStream_t stream) {
+  const bool split = split_k > 1;
+  const dim3 grid((N / BN) * (M / BM), 1, split ? split_k : batch), block(NTH);
   const bf16_t* a = static_cast<const bf16_t*>(A);
   const bf16_t* b = static_cast<const bf16_t*>(B);
   bf16_t* cp = static_cast<bf16_t*>(c_pre);
   const bf16_t* bi = static_cast<const bf16_t*>(bias);
-  if (split_k > 1) {
-    const int chunk = (K / split_k + BK - 1) / BK * BK;
-    dim3 gridk((N / BN) * (M / BM), 1, split_k);
-    hipLaunchKernelGGL((gemm256_kernel<0, true>), gridk, block, 0, stream,
-                       a, b, C, cp, bi, M, N, K, lda, ldb, ldc, stride_a,
-                       stride_b, stride_c, chunk);
-    return;
-  }
-  dim3 grid((N / BN) * (M / BM), 1, batch);
-#define G256(E)                                                             \
-  hipLaunchKernelGGL((gemm256_kernel<E>), grid, block, 0, stream, a, b, C, \
-                     cp, bi, M, N, K, lda, ldb, ldc, stride_a, stride_b,   \
-                     stride_c, 0)
-  switch (epi) {
-    case 0: G256(0); break;
-    case 1: G256(1); break;
-    case 2: G256(2); break;
-    case 3: G256(3); break;
-    case 4: G256(4); break;
-    default: throw std::runtime_error("bad epi");
+#define G256(E, F32)                                                        \
+  hipLaunchKernelGGL((gemm256_kernel<E, F32>), grid, block, 0, stream, a,  \
+                     b, C, cp, bi, M, N, K, lda, ldb, ldc, stride_a,       \
+                     stride_b, stride_c, k_chunk)
+  if (split) { G256(EPI_NONE, true); }
+  else switch (epi) {
+    case EPI_NONE: G256(EPI_NONE, false); break;
+    case EPI_BIAS: G256(EPI_BIAS, false); break;
+    case EPI_BIAS_GELU: G256(EPI_BIAS_GELU, false); break;
+    case EPI_GELU: G256(EPI_GELU, false); break;
+    case EPI_DGELU: G256(EPI_DGELU, false); break;
   }
 #undef G256
 }

@@ -1,0 +1,99 @@
+// Host-side plan of one hand GEMM call: which kernel runs it, into how many
+// K-chunks it splits and how long a chunk is. Plain C++17, no HIP include:
+// gemm_bf16 (gemm.hip) launches what this returns, the extension binds it
+// as `gemm_plan` for ops/hip.py, and a stand-alone host program can compile
+// it alone. Every dispatch and split-K decision of the hand path is here
+// and nowhere else.
+#pragma once
+
+#include <algorithm>
+#include <cstdint>
+
+namespace tepdist {
+
+struct GemmPlan {
+  int kernel;           // 256, 128, or 0 = no kernel accepts this call
+  int split_k;          // 1 = no split
+  int k_chunk;          // K elements per chunk; 0 when split_k == 1
+  const char* why_not;  // set when kernel == 0, else nullptr
+};
+
+// Epilogues of the hand GEMM (the `epi` argument). The only definition:
+// the kernels see it through gemm_tile.h.
+enum {
+  EPI_NONE = 0,
+  EPI_BIAS = 1,       // + bias
+  EPI_BIAS_GELU = 2,  // + bias, gelu; pre-activation written to c_pre
+  EPI_GELU = 3,       // gelu; pre-activation written to c_pre
+  // dgelu: C = (A@B) * gelu'(c_pre) — c_pre is the INPUT pre-activation
+  // saved by the forward (the fusion hipBLASLt has no algorithms for on
+  // gfx950, profiles/blaslt_epilogue_probe.md). 256 kernel only.
+  EPI_DGELU = 4
+};
+
+namespace plan {
+constexpr int T256 = 256;  // gemm256.hip tile (BM = BN)
+constexpr int T128 = 128;  // gemm.hip tile (BM = BN)
+constexpr int BK = 64;     // K-tile of both kernels
+constexpr int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+}  // namespace plan
+
+inline GemmPlan gemm_plan(int M, int N, int K, int lda, int ldb, bool a_kc,
+                          bool b_kc, int epi, int batch) {
+  using namespace plan;
+  if (epi < EPI_NONE || epi > EPI_DGELU)
+    return {0, 1, 0, "epi must be 0..4"};
+
+  // The 256 kernel's tiling applies to k-contiguous operands with whole
+  // tiles. Row alignment is NOT part of this test: it only decides below
+  // whether the 256 kernel accepts the call, so an unaligned canonical
+  // shape keeps the 256-tiling block count and runs on the 128 kernel.
+  const bool canon =
+      a_kc && b_kc && M % T256 == 0 && N % T256 == 0 && K % BK == 0;
+  const bool aligned = (lda & 7) == 0 && (ldb & 7) == 0;  // 16-byte rows
+  const int64_t blocks = canon ? int64_t(M / T256) * (N / T256)
+                               : cdiv(M, T128) * cdiv(N, T128);
+
+  // Split K when the (M, N) tile grid underfills the 256-CU chip and K is
+  // deep: aim at >= 512 blocks, prefer a whole number of 256-block
+  // generations so every CU stays busy to the end (48 blocks: x8 = 1.5
+  // generations -> x16 = 3 full), keep every chunk >= 2 K-tiles.
+  int split_k = 1, k_chunk = 0;
+  if (batch == 1 && epi == 0 && K >= 2048 && blocks < 384) {
+    const int b = static_cast<int>(blocks), max_by_k = K / (2 * BK);
+    int s = std::max(2, (512 + b - 1) / b);
+    for (int cand = s; cand < std::min(17, max_by_k + 1); ++cand)
+      if ((b * cand) % 256 == 0) {
+        s = cand;
+        break;
+      }
+    s = std::max(2, std::min({s, 16, max_by_k}));
+    // Normalize to the number of chunks that are not empty once the chunk
+    // is rounded up to whole K-tiles. This step rounds floor(K / s); when
+    // K is not a multiple of 64 that can be one tile shorter than the
+    // k_chunk below, and s = 16 then comes out as 17 (K = 2056: floor
+    // gives 128, ceil(2056 / 128) = 17). Harmless, since k_chunk is
+    // derived from the final count, and kept because changing it would
+    // change results; it never happens when K % 64 == 0.
+    const int64_t floor_chunk = cdiv(K / s, BK) * BK;
+    split_k = static_cast<int>(std::max<int64_t>(2, cdiv(K, floor_chunk)));
+    k_chunk = static_cast<int>(cdiv(cdiv(K, split_k), BK) * BK);
+  }
+
+  // The 256 kernel's pipeline needs >= 2 K-tiles in every chunk it runs,
+  // the last one included, and no empty chunk; under split it has only
+  // the plain epilogue.
+  bool ok256 = canon && aligned && K >= 2 * BK;
+  if (split_k > 1)
+    ok256 = ok256 && k_chunk >= 2 * BK && K % k_chunk != BK &&
+            cdiv(K, k_chunk) == split_k;
+  if (ok256) return {T256, split_k, k_chunk, nullptr};
+  if (epi == EPI_DGELU)
+    return {0, 1, 0,
+            "epi 4 (dgelu) runs only on the 256 kernel: k-contiguous "
+            "operands, M and N multiples of 256, K a multiple of 64 and "
+            ">= 128, 16-byte-aligned rows"};
+  return {T128, split_k, k_chunk, nullptr};
+}
+
+}  // namespace tepdist

@@ -14,25 +14,30 @@ using bf16 = __hip_bfloat16;
 //   a_kc: A stored row-major [M,K] (k-contiguous); else stored [K,M].
 //   b_kc: B stored row-major [N,K] (k-contiguous, i.e. the operand is a
 //         transposed weight W[N,K]); else stored [K,N].
-// epi: 0 = none, 1 = +bias, 2 = +bias+gelu (writes pre-act to c_pre),
-//      3 = gelu only (writes pre-act to c_pre).
+// epi (the EPI_* enum of gemm_plan.h): 0 = none, 1 = +bias, 2 = +bias+gelu
+//      (writes pre-act to c_pre), 3 = gelu only (writes pre-act to c_pre),
+//      4 = dgelu: C = (A @ B) * gelu'(c_pre), c_pre being the INPUT
+//      pre-activation saved by the forward.
 // Batched over `batch` with element strides; stride 0 broadcasts.
+// gemm_plan() (gemm_plan.h) decides the kernel and the K split from the
+// arguments alone; gemm_bf16 launches that plan and throws with the plan's
+// reason when no kernel accepts the call (epi 4 outside the 256 kernel's
+// case). When the plan splits K (split_k > 1), splitk_ws must hold
+// split_k * M * N floats and ldc must be N: the chunks write fp32 partials
+// there and a second launch reduces them into C. splitk_ws may be null
+// otherwise.
 void gemm_bf16(const void* A, const void* B, void* C, void* c_pre,
                const void* bias, int M, int N, int K, int lda, int ldb,
                int ldc, int64_t stride_a, int64_t stride_b, int64_t stride_c,
-               int batch, bool a_kc, bool b_kc, int epi, int split_k,
+               int batch, bool a_kc, bool b_kc, int epi, float* splitk_ws,
                hipStream_t stream);
-// Deep-pipelined 256x256 path for canonical (KC x KC, aligned) shapes.
-bool gemm256_supported(int M, int N, int K, int lda, int ldb, bool a_kc,
-                       bool b_kc, int epi, int split_k);
+// Launcher of the deep-pipelined 256x256 kernel, for gemm_bf16 only: runs
+// the plan it is given (split_k > 1: C is the fp32 workspace).
 void gemm256_bf16(const void* A, const void* B, void* C, void* c_pre,
                   const void* bias, int M, int N, int K, int lda, int ldb,
                   int ldc, int64_t stride_a, int64_t stride_b,
                   int64_t stride_c, int batch, int epi, int split_k,
-                  hipStream_t stream);
-// Reduce split-K fp32 partials [nparts, mn] into bf16 out [mn].
-void splitk_reduce(const float* parts, void* out, int nparts, int64_t mn,
-                   hipStream_t stream);
+                  int k_chunk, hipStream_t stream);
 
 // --- Transpose -------------------------------------------------------------
 // out[c][r] = in[r][c] per batch (strides in elements).

@@ -1,17 +1,31 @@
-// Swizzled LDS tile images shared by the flash-attention kernels and the
-// fragment probe in debug.hip.
+// Swizzled LDS tile images shared by the GEMM, transpose and flash-attention
+// kernels and the fragment probe in debug.hip.
 #pragma once
 
 #include "common.h"
 
 namespace tepdist {
 
-// LDS addressing for a [rows][C] bf16 image, C in {64,128}: XOR swizzle of
-// the 16B column slot by bit-reversed (row>>1) (see gemm.hip).
+// The swizzle: a row's 16B column slots are XORed with x(row) = the
+// bit-reversed (row>>1)&7. The bit reversal puts the fragment-read service
+// groups' row bit (row bit 1 under quad-strided 16-lane grouping, row bits
+// 1..3 under contiguous grouping) into slot bits that the reads' own column
+// spread does not already cover, making ds_read_b128 column reads
+// conflict-free; writes stay <=2-way.
+// A macro on purpose: as a function LLVM simplifies it on its own before
+// inlining (it recognises the bit reversal), and the global_load_lds
+// staging sites, which fold it into the thread-index shifts instead, come
+// out with different address code and register counts.
+#define SWZ8(row)                                     \
+  ({                                                  \
+    const int r1_ = (row) >> 1;                       \
+    ((r1_ & 1) << 2) | (r1_ & 2) | ((r1_ >> 2) & 1);  \
+  })
+
+// LDS addressing for a [rows][C] bf16 image of unpadded rows, C in {64,128}.
 template <int C>
 DEV_INLINE int loff(int row, int col_e) {
-  const int r1 = row >> 1;
-  const int x = ((r1 & 1) << 2) | (r1 & 2) | ((r1 >> 2) & 1);
+  const int x = SWZ8(row);
   return row * C + (col_e ^ ((x << 3) & (C - 1)));
 }
 

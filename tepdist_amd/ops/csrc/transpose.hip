@@ -9,6 +9,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "lds_frag.h"
 
 namespace tepdist {
 
@@ -118,11 +119,7 @@ void transpose_kernel(const bf16_t* __restrict__ in,
 // canonicalization transposes); the generic kernel covers the rest.
 constexpr int T2 = 128;
 
-DEV_INLINE int t2off(int row, int col_e) {  // loff for a [.][128] image
-  const int r1 = row >> 1;
-  const int x = ((r1 & 1) << 2) | (r1 & 2) | ((r1 >> 2) & 1);
-  return row * T2 + (col_e ^ ((x << 3) & 127));
-}
+DEV_INLINE int t2off(int row, int col_e) { return loff<T2>(row, col_e); }
 
 template <bool GELUG, bool NAT>
 __launch_bounds__(NT) __global__

@@ -106,35 +106,14 @@ def _gemm_raw(a: torch.Tensor, b_stored: torch.Tensor, a_kc: bool, b_kc: bool,
     if epi >= 2 and cp is None:
         cp = torch.empty_like(c)
 
-    # split-K when the (M,N) tile grid underfills the 256-CU chip and K deep
-    if a_kc and b_kc and M % 256 == 0 and N % 256 == 0 and K % 64 == 0:
-        blocks = (M // 256) * (N // 256)
-    else:
-        blocks = ((M + 127) // 128) * ((N + 127) // 128)
-    if batch == 1 and epi == 0 and K >= 2048 and blocks < 384:
-        split_k = max(2, (512 + blocks - 1) // blocks)
-        # prefer a whole number of 256-block generations so every CU stays
-        # busy to the end (e.g. 48 blocks: x8 = 1.5 waves -> x16 = 3 full)
-        for cand in range(split_k, min(17, K // 128 + 1)):
-            if (blocks * cand) % 256 == 0:
-                split_k = cand
-                break
-        split_k = max(2, min(split_k, 16, K // 128))
-        # normalize to the EFFECTIVE chunk count: the kernel rounds the
-        # chunk up to a 64-multiple, which can leave trailing z-blocks
-        # with no K range at all (their prologue would read past K)
-        chunk = (K // split_k + 63) // 64 * 64
-        split_k = max(2, -(-K // chunk))
-        parts = torch.empty(split_k, M * N, dtype=torch.float32, device=dev)
-        ext.gemm(a.data_ptr(), b_stored.data_ptr(), parts.data_ptr(), 0, 0,
-                 M, N, K, lda, ldb, N, 0, 0, M * N, 1, a_kc, b_kc, 0,
-                 split_k, _stream())
-        ext.splitk_reduce(parts.data_ptr(), c.data_ptr(), split_k, M * N,
-                          _stream())
-        return c, cp
+    # kernel choice and split-K are planned in csrc/gemm_plan.h; a split
+    # plan needs fp32 room for its partials (ext.gemm reduces them into c)
+    split_k = ext.gemm_plan(M, N, K, lda, ldb, a_kc, b_kc, epi, batch)[1]
+    ws = torch.empty(split_k * M * N, dtype=torch.float32, device=dev) \
+        if split_k > 1 else None
     ext.gemm(a.data_ptr(), b_stored.data_ptr(), c.data_ptr(), _p(cp), _p(bias),
-             M, N, K, lda, ldb, N, sa, sb, M * N, batch, a_kc, b_kc, epi, 1,
-             _stream())
+             M, N, K, lda, ldb, N, sa, sb, M * N, batch, a_kc, b_kc, epi,
+             _p(ws), _stream())
     return c, cp
 
 
@@ -167,6 +146,17 @@ def linear_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor],
 
     fn = _pick_backend(("lin_f", M, N, K, epi), _hip, _blt)
     return fn()
+
+
+def _bias_sum(t: torch.Tensor) -> torch.Tensor:
+    """Column sums of contiguous t [rows, cols] as bf16 [cols] (the bias
+    gradient), accumulated in a zeroed fp32 workspace."""
+    rows, cols = t.shape
+    db = torch.empty(cols, dtype=BF16, device=t.device)
+    ws = torch.zeros(cols, dtype=torch.float32, device=t.device)
+    ext.bias_sum(t.data_ptr(), db.data_ptr(), ws.data_ptr(), rows, cols,
+                 _stream())
+    return db
 
 
 def gelu_fwd(x: torch.Tensor) -> torch.Tensor:
@@ -275,11 +265,7 @@ def mlp_bwd(dy, x, w1, w2, h, pre):
         # yields dgelu'd dh AND the fc bias grad
         dh, db1 = _blt_mlp_dgelu(dy, w2, pre)
         dw2 = torch.matmul(dy.t(), h)
-        db2 = torch.empty(dy.shape[1], dtype=BF16, device=dy.device)
-        ws = torch.zeros(dy.shape[1], dtype=torch.float32,
-                         device=dy.device)
-        ext.bias_sum(dy.data_ptr(), db2.data_ptr(), ws.data_ptr(),
-                     dy.shape[0], dy.shape[1], _stream())
+        db2 = _bias_sum(dy)
         dx, dw1, _ = linear_bwd(dh, x, w1, False, "none", None)
         out["r"] = (dx, dw1, db1, dw2, db2)
 
@@ -300,23 +286,19 @@ def mlp_bwd(dy, x, w1, w2, h, pre):
         w2T = transpose2d(w2)                       # [4d, d] KC
         dh, _ = _gemm_raw(dy, w2T, True, True, M, K2, N2, N2, N2, 0, 0, 1,
                           epi=4, out_pre=pre)
-        db1 = torch.empty(K2, dtype=BF16, device=dy.device)
-        ws = torch.zeros(K2, dtype=torch.float32, device=dy.device)
-        ext.bias_sum(dh.data_ptr(), db1.data_ptr(), ws.data_ptr(), M, K2,
-                     _stream())
+        db1 = _bias_sum(dh)
         dw2 = torch.matmul(dy.t(), h)
-        db2 = torch.empty(N2, dtype=BF16, device=dy.device)
-        ws2 = torch.zeros(N2, dtype=torch.float32, device=dy.device)
-        ext.bias_sum(dy.data_ptr(), db2.data_ptr(), ws2.data_ptr(), M, N2,
-                     _stream())
+        db2 = _bias_sum(dy)
         dx, dw1, _ = linear_bwd(dh, x, w1, False, "none", None)
         out["r"] = (dx, dw1, db1, dw2, db2)
 
     def _base():
-        # hand-dgelu vs composed, measured per shape (256-schedule shapes
-        # only; TEPDIST_GEMM_BACKEND pins propagate through _pick_backend)
-        if (dy.shape[0] % 256 == 0 and w2.shape[1] % 256 == 0
-                and dy.shape[1] % 64 == 0 and dy.shape[1] >= 128
+        # hand-dgelu vs composed, measured per shape (only where the plan
+        # gives the dgelu epilogue, epi 4, a kernel; TEPDIST_GEMM_BACKEND
+        # pins propagate through _pick_backend)
+        M, N2 = dy.shape
+        K2 = w2.shape[1]
+        if (ext.gemm_plan(M, K2, N2, N2, N2, True, True, 4, 1)[0] == 256
                 and pre.is_contiguous()):
             _pick_backend(("mlp_bh", dy.shape[0], dy.shape[1],
                            w2.shape[1]), _hand_dgelu, _composed)()
@@ -398,10 +380,7 @@ def linear_bwd(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor,
     dx, dw, dy_eff = fn()
     db = None
     if has_bias:
-        db = torch.empty(N, dtype=BF16, device=dy.device)
-        ws = torch.zeros(N, dtype=torch.float32, device=dy.device)
-        ext.bias_sum(dy_eff.data_ptr(), db.data_ptr(), ws.data_ptr(), M, N,
-                     _stream())
+        db = _bias_sum(dy_eff)
     return dx, dw, db
 
 

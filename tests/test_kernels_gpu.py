@@ -33,6 +33,22 @@ def _assert_close_bf16(ours, ref32, atol=2e-2, rtol=2e-2, scale=None):
 # --------------------------------------------------------------------------
 
 
+@pytest.fixture
+def hand_gemm():
+    """Pin the GEMM sites to the hand kernels: in the default "auto" mode
+    _pick_backend returns the output of whichever of the hand kernel and
+    hipBLASLt was faster, which need not be the hand kernel's."""
+    old = hip._GEMM_BACKEND
+    hip._GEMM_BACKEND = "hip"
+    yield
+    hip._GEMM_BACKEND = old
+
+
+def _plan(M, N, K, lda, ldb, a_kc=True, b_kc=True, epi=0, batch=1):
+    return hip.ext.gemm_plan(M, N, K, lda, ldb, a_kc, b_kc, epi, batch)
+
+
+@pytest.mark.usefixtures("hand_gemm")
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (200, 136, 72),
                                    (256, 512, 1024), (33, 17, 9)])
 def test_gemm_nt_layout(M, N, K):
@@ -45,6 +61,7 @@ def test_gemm_nt_layout(M, N, K):
     _assert_close_bf16(y, ref, rtol=3e-2, scale=math.sqrt(K))
 
 
+@pytest.mark.usefixtures("hand_gemm")
 @pytest.mark.parametrize("ta,tb", [(False, False), (False, True),
                                    (True, False)])
 def test_gemm_transposes(ta, tb):
@@ -59,6 +76,7 @@ def test_gemm_transposes(ta, tb):
     _assert_close_bf16(c, ref, rtol=3e-2, scale=math.sqrt(K))
 
 
+@pytest.mark.usefixtures("hand_gemm")
 @pytest.mark.parametrize("M,N,K", [(512, 256, 8192), (256, 256, 4096),
                                    (768, 512, 16384), (3072, 768, 2048),
                                    (768, 768, 2048), (2304, 768, 2048)])
@@ -73,6 +91,7 @@ def test_gemm_splitk_256(M, N, K):
     _assert_close_bf16(y, ref, rtol=3e-2, scale=math.sqrt(K))
 
 
+@pytest.mark.usefixtures("hand_gemm")
 def test_gemm_batched():
     B, M, N, K = 6, 64, 96, 32
     a = _randn(B, M, K, seed=5)
@@ -83,6 +102,7 @@ def test_gemm_batched():
     _assert_close_bf16(c, ref, rtol=3e-2, scale=math.sqrt(K))
 
 
+@pytest.mark.usefixtures("hand_gemm")
 def test_linear_bias_gelu():
     M, N, K = 128, 96, 64
     x = _randn(M, K, seed=7)
@@ -96,6 +116,7 @@ def test_linear_bias_gelu():
     _assert_close_bf16(y, y_ref, rtol=3e-2, scale=math.sqrt(K))
 
 
+@pytest.mark.usefixtures("hand_gemm")
 def test_linear_bwd():
     M, N, K = 192, 80, 112
     x = _randn(M, K, seed=10)
@@ -108,6 +129,65 @@ def test_linear_bwd():
     _assert_close_bf16(dw, dy.float().t() @ x.float(), rtol=3e-2,
                        scale=math.sqrt(M))
     _assert_close_bf16(db, dy.float().sum(0), rtol=3e-2, scale=math.sqrt(M))
+
+
+# Plan branches (csrc/gemm_plan.h) that the shapes above do not reach. Each
+# test first asserts the plan, so that it keeps covering its branch.
+
+@pytest.mark.usefixtures("hand_gemm")
+def test_gemm_splitk_128_by_layout():
+    # k-outermost operands: split-K on the 128 kernel's register-transpose
+    # staging
+    M, N, K = 128, 128, 2048
+    assert _plan(M, N, K, M, N, False, False)[:3] == (128, 16, 128)
+    a = _randn(K, M, seed=41).t()
+    b = _randn(K, N, seed=42)
+    c = hip.matmul(a, b)
+    torch.cuda.synchronize()
+    _assert_close_bf16(c, a.float() @ b.float(), rtol=3e-2,
+                       scale=math.sqrt(K))
+
+
+@pytest.mark.usefixtures("hand_gemm")
+@pytest.mark.parametrize("K,plan", [
+    (2176, (128, 12, 192)),   # last chunk is one K-tile: 256 kernel refuses
+    (2048, (256, 16, 128))])  # the smallest split the 256 kernel runs
+def test_gemm_splitk_canonical_edges(K, plan):
+    M, N = 256, 256
+    assert _plan(M, N, K, K, K)[:3] == plan
+    a = _randn(M, K, seed=43)
+    b = _randn(N, K, seed=44)
+    y = hip.matmul(a, b.t())
+    torch.cuda.synchronize()
+    _assert_close_bf16(y, a.float() @ b.float().t(), rtol=3e-2,
+                       scale=math.sqrt(K))
+
+
+@pytest.mark.usefixtures("hand_gemm")
+def test_gemm_splitk_k_tail_17_chunks():
+    # K is no multiple of 64: 17 chunks of 128, the last one 8 long
+    M, N, K = 120, 136, 2056
+    assert _plan(M, N, K, K, K)[:3] == (128, 17, 128)
+    x = _randn(M, K, seed=45)
+    w = _randn(N, K, seed=46)
+    y, _ = hip.linear_fwd(x, w, None, "none")
+    torch.cuda.synchronize()
+    _assert_close_bf16(y, x.float() @ w.float().t(), rtol=3e-2,
+                       scale=math.sqrt(K))
+
+
+def test_gemm_dgelu_rejected_with_plan_reason():
+    # epi 4 exists on the 256 kernel only; nothing is launched
+    M, N, K = 500, 256, 128
+    kernel, _, _, why = _plan(M, N, K, K, K, epi=4)
+    assert kernel == 0 and why
+    a = _randn(M, K, seed=47)
+    b = _randn(N, K, seed=48)
+    pre = _randn(M, N, seed=49)
+    with pytest.raises(RuntimeError) as exc:
+        hip._gemm_raw(a, b, True, True, M, N, K, K, K, 0, 0, 1, epi=4,
+                      out_pre=pre)
+    assert why in str(exc.value)
 
 
 # --------------------------------------------------------------------------
