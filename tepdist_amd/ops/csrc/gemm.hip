@@ -22,8 +22,9 @@
 //    addressed it as element lane&15 of row lane>>4; those unaligned
 //    addresses collapse to the quad leaders' 8B words, which is why it saw
 //    only 16 distinct values per group and this path took the register
-//    transpose. The GEMM has not been re-measured with the right
-//    addressing.)
+//    transpose. The 256 kernel now reads two k-outer operands that way,
+//    gemm256.hip; this kernel keeps the register transpose, which also
+//    serves mixed layouts, partial tiles and unaligned rows.)
 //
 // Replaces the reference's XLA-codegen GEMMs (all device code
 // in TePDist is XLA-generated PTX; here it is hand-written CDNA4).
@@ -377,7 +378,8 @@ void gemm_bf16(const void* A, const void* B, void* C, void* c_pre,
 
   if (p.kernel == plan::T256) {
     gemm256_bf16(A, B, out, c_pre, bias, M, N, K, lda, ldb, ldc, stride_a,
-                 stride_b, stride_c, batch, epi, p.split_k, p.k_chunk, stream);
+                 stride_b, stride_c, batch, /*k_outer=*/!a_kc, epi, p.split_k,
+                 p.k_chunk, stream);
   } else {
     const int nbx = (N + BN - 1) / BN, nby = (M + BM - 1) / BM;
     const dim3 grid(nbx * nby, 1, split ? p.split_k : batch), block(NTHREADS);

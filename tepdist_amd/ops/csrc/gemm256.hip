@@ -18,10 +18,22 @@
 // single counted s_waitcnt vmcnt(6) + barrier per K-tile boundary keeps 6
 // quarter-units (3 "half-tiles") in flight.
 //
-// Handles only the canonical case (both operands k-contiguous, M,N % 256
-// == 0, K % 64 == 0, 16B-aligned rows, >= 2 K-tiles per chunk); gemm_plan.h
-// decides when that holds, gemm.hip covers the rest and linear_bwd
-// canonicalizes dgrad/wgrad into this case via transposes.
+// Two operand layouts, both with M,N % 256 == 0, K % 64 == 0, 16B-aligned
+// rows and >= 2 K-tiles per chunk (gemm_plan.h decides when that holds,
+// gemm.hip covers the rest):
+//  - canonical: both operands k-contiguous (A [M][K], B [N][K]);
+//  - k-outer (KO = true): both operands stored [K][F] (A [K][M], B [K][N]),
+//    wgrad's dy and x as they lie in memory. A quarter unit is then the
+//    natural [64 k][64 f] image, staged by the same stage_q with the row
+//    and column roles swapped, and the fragments are read with the map of
+//    tr_frag<BK> (lds_frag.h; two ds_read_b64_tr_b16 each, conflict-free
+//    at 64-column rows). That map permutes k within each 32-block; both
+//    operands go through it, so the products pair up unchanged. Schedule,
+//    slots, barriers, split-K and epilogues are the canonical ones.
+// Mixed layouts (dgrad's weight) are not handled: linear_bwd transposes the
+// weight, a few microseconds.
+
+#include <stdexcept>
 
 #include "common.h"
 #include "gemm_tile.h"
@@ -40,7 +52,8 @@ constexpr int SLOT_E = QROWS * BK; // elements per slot (8 KiB)
 DEV_INLINE int qoff(int row, int col_e) { return loff<BK>(row, col_e); }
 
 // stage one quarter unit: rows [f0, f0+64) x cols [k0, k0+64) of a
-// k-contiguous operand into slot `dst` (one glds dwordx4 per thread).
+// k-contiguous operand into slot `dst` (one glds dwordx4 per thread). A
+// k-outer operand passes (k0, f0) instead: rows are k, columns features.
 DEV_INLINE void stage_q(const bf16_t* __restrict__ src, int64_t ld, int f0,
                         int k0, bf16_t* dst) {
   const int wave = threadIdx.x >> 6;
@@ -61,10 +74,67 @@ DEV_INLINE bf16x8 fragq(const bf16_t* slot, int row, int col_e) {
   return *reinterpret_cast<const bf16x8*>(slot + qoff(row, col_e));
 }
 
+// tr_frag<BK> (lds_frag.h: same lanes, same addresses, same k order) with
+// its two ds_read_b64_tr_b16 written as inline asm. Through the builtin the
+// compiler takes the read for an ordinary load beside the in-flight
+// global_load_lds DMAs and puts s_waitcnt vmcnt(0) in front of every group
+// of reads, which drains the counted-vmcnt(6) pipeline four times per
+// K-tile. The compiler does not count these reads, so the caller waits
+// lgkmcnt(0) itself before the first use (LGKM_WAIT_KO below). The k half
+// KK and the +16-row second read are immediate offsets: the swizzle only
+// looks at row bits 1..3.
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) const bf16_t* lds_cptr_t;
+
+template <int OFF>
+DEV_INLINE bf16x4 tr_read_asm(uint32_t addr) {
+  u32x2 v;
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2"
+               : "=v"(v)
+               : "v"(addr), "n"(OFF)
+               : "memory");
+  return __builtin_bit_cast(bf16x4, v);
+}
+
+template <int KK>
+DEV_INLINE bf16x8 tr_frag_asm(const bf16_t* slot, int df, int lane) {
+  const int i = lane & 15, g = lane >> 4;
+  const uint32_t addr = (uint32_t)(uintptr_t)(lds_cptr_t)(
+      slot + qoff(4 * g + (i >> 2), 16 * df + 4 * (i & 3)));
+  const bf16x4 lo = tr_read_asm<KK * 32 * BK * 2>(addr);
+  const bf16x4 hi = tr_read_asm<(KK * 32 + 16) * BK * 2>(addr);
+  bf16x8 f;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    f[e] = lo[e];
+    f[e + 4] = hi[e];
+  }
+  return f;
+}
+
+// MFMA fragment of 16 features x 32 k from one slot: feature block df
+// (0..3), k half KK (0..1). Canonical slots are [f][k] images, k-outer ones
+// [k][f] read transposed. Wave-uniform call sites only (the transposed read
+// gathers across all 64 lanes).
+template <bool KO, int KK>
+DEV_INLINE bf16x8 frag_fk(const bf16_t* slot, int df, int lane) {
+  if (KO) return tr_frag_asm<KK>(slot, df, lane);
+  return fragq(slot, df * 16 + (lane & 15), 8 * (lane >> 4) + 32 * KK);
+}
+
 #define RAW_BAR() __builtin_amdgcn_s_barrier()
 #define VMCNT6() asm volatile("s_waitcnt vmcnt(6)" ::: "memory")
+// k-outer fragments come from inline-asm reads: wait for them by hand, and
+// keep the scheduler from lifting the register-only MFMAs over the wait.
+#define LGKM_WAIT_KO()                                      \
+  do {                                                      \
+    if (KO) {                                               \
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    \
+      __builtin_amdgcn_sched_barrier(0);                    \
+    }                                                       \
+  } while (0)
 
-template <int EPI, bool F32OUT = false>
+template <int EPI, bool F32OUT = false, bool KO = false>
 __launch_bounds__(NTH, 1) __global__
 void gemm256_kernel(const bf16_t* __restrict__ A,
                     const bf16_t* __restrict__ B, void* __restrict__ Cv,
@@ -103,17 +173,20 @@ void gemm256_kernel(const bf16_t* __restrict__ A,
 
   const int nk = (kend - kbeg) / BK;
 
-  // A quarter q of tile t covers rows m0 + 64q; B quarter: n0 + 64q.
+  // A quarter q of tile t covers features m0 + 64q; B quarter: n0 + 64q.
+  auto stage_1 = [&](const bf16_t* __restrict__ src, int ld, int f0, int t,
+                     bf16_t* dst) {
+    if (KO) stage_q(src, ld, kbeg + t * BK, f0, dst);
+    else    stage_q(src, ld, f0, kbeg + t * BK, dst);
+  };
   auto stage_a = [&](int t, int q2) {  // stage quarters q2 and q2+1
-    stage_q(A, lda, m0 + 64 * q2, kbeg + t * BK,
-            aslot + ((4 * t + q2) & 7) * SLOT_E);
-    stage_q(A, lda, m0 + 64 * (q2 + 1), kbeg + t * BK,
+    stage_1(A, lda, m0 + 64 * q2, t, aslot + ((4 * t + q2) & 7) * SLOT_E);
+    stage_1(A, lda, m0 + 64 * (q2 + 1), t,
             aslot + ((4 * t + q2 + 1) & 7) * SLOT_E);
   };
   auto stage_b = [&](int t, int q2) {
-    stage_q(B, ldb, n0 + 64 * q2, kbeg + t * BK,
-            bslot + ((4 * t + q2) & 7) * SLOT_E);
-    stage_q(B, ldb, n0 + 64 * (q2 + 1), kbeg + t * BK,
+    stage_1(B, ldb, n0 + 64 * q2, t, bslot + ((4 * t + q2) & 7) * SLOT_E);
+    stage_1(B, ldb, n0 + 64 * (q2 + 1), t,
             bslot + ((4 * t + q2 + 1) & 7) * SLOT_E);
   };
 
@@ -150,20 +223,18 @@ void gemm256_kernel(const bf16_t* __restrict__ A,
 #pragma unroll
       for (int mi = 0; mi < 8; ++mi) {
         const bf16_t* s = (mi < 4) ? as0 : as1;
-        const int row = (mi & 3) * 16 + (lane & 15);
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-          af[mi][kk] = fragq(s, row, 8 * (lane >> 4) + 32 * kk);
+        af[mi][0] = frag_fk<KO, 0>(s, mi & 3, lane);
+        af[mi][1] = frag_fk<KO, 1>(s, mi & 3, lane);
       }
       bf16x8 bf0[2];
       {
         const bf16_t* bs = bslot + ((4 * t + 0) & 7) * SLOT_E;
-        const int row = wn * 16 + (lane & 15);
-        bf0[0] = fragq(bs, row, 8 * (lane >> 4));
-        bf0[1] = fragq(bs, row, 8 * (lane >> 4) + 32);
+        bf0[0] = frag_fk<KO, 0>(bs, wn, lane);
+        bf0[1] = frag_fk<KO, 1>(bs, wn, lane);
       }
       if (t + 1 < nk) stage_b(t + 1, 2);
       RAW_BAR();
+      LGKM_WAIT_KO();
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int mi = 0; mi < 8; ++mi)
@@ -180,14 +251,14 @@ void gemm256_kernel(const bf16_t* __restrict__ A,
       bf16x8 bfp[2];
       {
         const bf16_t* bs = bslot + ((4 * t + p) & 7) * SLOT_E;
-        const int row = wn * 16 + (lane & 15);
-        bfp[0] = fragq(bs, row, 8 * (lane >> 4));
-        bfp[1] = fragq(bs, row, 8 * (lane >> 4) + 32);
+        bfp[0] = frag_fk<KO, 0>(bs, wn, lane);
+        bfp[1] = frag_fk<KO, 1>(bs, wn, lane);
       }
       if (p == 1 && t + 2 < nk) stage_a(t + 2, 0);
       if (p == 2 && t + 2 < nk) stage_a(t + 2, 2);
       if (p == 3 && t + 2 < nk) stage_b(t + 2, 0);
       RAW_BAR();
+      LGKM_WAIT_KO();
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int mi = 0; mi < 8; ++mi)
@@ -296,28 +367,35 @@ void gemm256_kernel(const bf16_t* __restrict__ A,
 
 // Launches what gemm_plan() planned for the 256 kernel: split_k > 1 writes
 // fp32 partials (C is then the workspace), chunk z at C + z*stride_c.
+// k_outer: both operands stored [K][F] (plain epilogue only).
 void gemm256_bf16(const void* A, const void* B, void* C, void* c_pre,
                   const void* bias, int M, int N, int K, int lda, int ldb,
                   int ldc, int64_t stride_a, int64_t stride_b,
-                  int64_t stride_c, int batch, int epi, int split_k,
-                  int k_chunk, hipStream_t stream) {
+                  int64_t stride_c, int batch, bool k_outer, int epi,
+                  int split_k, int k_chunk, hipStream_t stream) {
   const bool split = split_k > 1;
   const dim3 grid((N / BN) * (M / BM), 1, split ? split_k : batch), block(NTH);
   const bf16_t* a = static_cast<const bf16_t*>(A);
   const bf16_t* b = static_cast<const bf16_t*>(B);
   bf16_t* cp = static_cast<bf16_t*>(c_pre);
   const bf16_t* bi = static_cast<const bf16_t*>(bias);
-#define G256(E, F32)                                                        \
-  hipLaunchKernelGGL((gemm256_kernel<E, F32>), grid, block, 0, stream, a,  \
-                     b, C, cp, bi, M, N, K, lda, ldb, ldc, stride_a,       \
+#define G256(E, F32, KO)                                                    \
+  hipLaunchKernelGGL((gemm256_kernel<E, F32, KO>), grid, block, 0, stream, \
+                     a, b, C, cp, bi, M, N, K, lda, ldb, ldc, stride_a,    \
                      stride_b, stride_c, k_chunk)
-  if (split) { G256(EPI_NONE, true); }
+  if (k_outer) {
+    if (epi != EPI_NONE)
+      throw std::runtime_error(
+          "gemm256_bf16: k-outer operands have only the plain epilogue");
+    if (split) { G256(EPI_NONE, true, true); }
+    else { G256(EPI_NONE, false, true); }
+  } else if (split) { G256(EPI_NONE, true, false); }
   else switch (epi) {
-    case EPI_NONE: G256(EPI_NONE, false); break;
-    case EPI_BIAS: G256(EPI_BIAS, false); break;
-    case EPI_BIAS_GELU: G256(EPI_BIAS_GELU, false); break;
-    case EPI_GELU: G256(EPI_GELU, false); break;
-    case EPI_DGELU: G256(EPI_DGELU, false); break;
+    case EPI_NONE: G256(EPI_NONE, false, false); break;
+    case EPI_BIAS: G256(EPI_BIAS, false, false); break;
+    case EPI_BIAS_GELU: G256(EPI_BIAS_GELU, false, false); break;
+    case EPI_GELU: G256(EPI_GELU, false, false); break;
+    case EPI_DGELU: G256(EPI_DGELU, false, false); break;
   }
 #undef G256
 }

@@ -38,27 +38,15 @@ constexpr int BK = 64;     // K-tile of both kernels
 constexpr int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 }  // namespace plan
 
-inline GemmPlan gemm_plan(int M, int N, int K, int lda, int ldb, bool a_kc,
-                          bool b_kc, int epi, int batch) {
-  using namespace plan;
-  if (epi < EPI_NONE || epi > EPI_DGELU)
-    return {0, 1, 0, "epi must be 0..4"};
-
-  // The 256 kernel's tiling applies to k-contiguous operands with whole
-  // tiles. Row alignment is NOT part of this test: it only decides below
-  // whether the 256 kernel accepts the call, so an unaligned canonical
-  // shape keeps the 256-tiling block count and runs on the 128 kernel.
-  const bool canon =
-      a_kc && b_kc && M % T256 == 0 && N % T256 == 0 && K % BK == 0;
-  const bool aligned = (lda & 7) == 0 && (ldb & 7) == 0;  // 16-byte rows
-  const int64_t blocks = canon ? int64_t(M / T256) * (N / T256)
-                               : cdiv(M, T128) * cdiv(N, T128);
-
-  // Split K when the (M, N) tile grid underfills the 256-CU chip and K is
-  // deep: aim at >= 512 blocks, prefer a whole number of 256-block
-  // generations so every CU stays busy to the end (48 blocks: x8 = 1.5
-  // generations -> x16 = 3 full), keep every chunk >= 2 K-tiles.
-  int split_k = 1, k_chunk = 0;
+namespace plan {
+// Split K when the (M, N) tile grid underfills the 256-CU chip and K is
+// deep: aim at >= 512 blocks, prefer a whole number of 256-block
+// generations so every CU stays busy to the end (48 blocks: x8 = 1.5
+// generations -> x16 = 3 full), keep every chunk >= 2 K-tiles.
+inline void split_for(int64_t blocks, int K, int epi, int batch,
+                      int* split_k, int* k_chunk) {
+  *split_k = 1;
+  *k_chunk = 0;
   if (batch == 1 && epi == 0 && K >= 2048 && blocks < 384) {
     const int b = static_cast<int>(blocks), max_by_k = K / (2 * BK);
     int s = std::max(2, (512 + b - 1) / b);
@@ -76,18 +64,55 @@ inline GemmPlan gemm_plan(int M, int N, int K, int lda, int ldb, bool a_kc,
     // derived from the final count, and kept because changing it would
     // change results; it never happens when K % 64 == 0.
     const int64_t floor_chunk = cdiv(K / s, BK) * BK;
-    split_k = static_cast<int>(std::max<int64_t>(2, cdiv(K, floor_chunk)));
-    k_chunk = static_cast<int>(cdiv(cdiv(K, split_k), BK) * BK);
+    *split_k = static_cast<int>(std::max<int64_t>(2, cdiv(K, floor_chunk)));
+    *k_chunk = static_cast<int>(cdiv(cdiv(K, *split_k), BK) * BK);
+  }
+}
+
+// The 256 kernel's pipeline needs >= 2 K-tiles in every chunk it runs, the
+// last one included, and no empty chunk.
+inline bool chunks_fit_256(int K, int split_k, int k_chunk) {
+  if (K < 2 * BK) return false;
+  if (split_k == 1) return true;
+  return k_chunk >= 2 * BK && K % k_chunk != BK &&
+         cdiv(K, k_chunk) == split_k;
+}
+}  // namespace plan
+
+inline GemmPlan gemm_plan(int M, int N, int K, int lda, int ldb, bool a_kc,
+                          bool b_kc, int epi, int batch) {
+  using namespace plan;
+  if (epi < EPI_NONE || epi > EPI_DGELU)
+    return {0, 1, 0, "epi must be 0..4"};
+
+  // The 256 kernel's tiling applies to whole tiles of two k-contiguous
+  // operands. Row alignment is NOT part of this test: it only decides below
+  // whether the 256 kernel accepts the call, so an unaligned canonical
+  // shape keeps the 256-tiling block count and runs on the 128 kernel.
+  const bool tiled = M % T256 == 0 && N % T256 == 0 && K % BK == 0;
+  const bool canon = a_kc && b_kc && tiled;
+  const bool aligned = (lda & 7) == 0 && (ldb & 7) == 0;  // 16-byte rows
+  int split_k, k_chunk;
+
+  // Two k-outer operands (wgrad: A stored [K][M], B stored [K][N]) run on
+  // the 256 kernel in place, plain epilogue only, under the canonical
+  // case's conditions and with its block count and split. A k-outer call
+  // that misses any of them is planned below exactly as it always was.
+  if (!a_kc && !b_kc && tiled && aligned && epi == EPI_NONE) {
+    split_for(int64_t(M / T256) * (N / T256), K, epi, batch, &split_k,
+              &k_chunk);
+    if (chunks_fit_256(K, split_k, k_chunk))
+      return {T256, split_k, k_chunk, nullptr};
   }
 
-  // The 256 kernel's pipeline needs >= 2 K-tiles in every chunk it runs,
-  // the last one included, and no empty chunk; under split it has only
-  // the plain epilogue.
-  bool ok256 = canon && aligned && K >= 2 * BK;
-  if (split_k > 1)
-    ok256 = ok256 && k_chunk >= 2 * BK && K % k_chunk != BK &&
-            cdiv(K, k_chunk) == split_k;
-  if (ok256) return {T256, split_k, k_chunk, nullptr};
+  const int64_t blocks = canon ? int64_t(M / T256) * (N / T256)
+                               : cdiv(M, T128) * cdiv(N, T128);
+  split_for(blocks, K, epi, batch, &split_k, &k_chunk);
+
+  // Under split the 256 kernel has only the plain epilogue (split_for
+  // never splits another).
+  if (canon && aligned && chunks_fit_256(K, split_k, k_chunk))
+    return {T256, split_k, k_chunk, nullptr};
   if (epi == EPI_DGELU)
     return {0, 1, 0,
             "epi 4 (dgelu) runs only on the 256 kernel: k-contiguous "

@@ -32,12 +32,13 @@ void gemm_bf16(const void* A, const void* B, void* C, void* c_pre,
                int batch, bool a_kc, bool b_kc, int epi, float* splitk_ws,
                hipStream_t stream);
 // Launcher of the deep-pipelined 256x256 kernel, for gemm_bf16 only: runs
-// the plan it is given (split_k > 1: C is the fp32 workspace).
+// the plan it is given (split_k > 1: C is the fp32 workspace). k_outer:
+// both operands stored [K][F] (a_kc = b_kc = false), epi 0 only.
 void gemm256_bf16(const void* A, const void* B, void* C, void* c_pre,
                   const void* bias, int M, int N, int K, int lda, int ldb,
                   int ldc, int64_t stride_a, int64_t stride_b,
-                  int64_t stride_c, int batch, int epi, int split_k,
-                  int k_chunk, hipStream_t stream);
+                  int64_t stride_c, int batch, bool k_outer, int epi,
+                  int split_k, int k_chunk, hipStream_t stream);
 
 // --- Transpose -------------------------------------------------------------
 // out[c][r] = in[r][c] per batch (strides in elements).

@@ -264,7 +264,7 @@ def mlp_bwd(dy, x, w1, w2, h, pre):
         # proj dgrad with the DGELU_BGRAD epilogue: one library call
         # yields dgelu'd dh AND the fc bias grad
         dh, db1 = _blt_mlp_dgelu(dy, w2, pre)
-        dw2 = torch.matmul(dy.t(), h)
+        dw2 = matmul(dy.t(), h)      # measured: in-place hand wgrad or library
         db2 = _bias_sum(dy)
         dx, dw1, _ = linear_bwd(dh, x, w1, False, "none", None)
         out["r"] = (dx, dw1, db1, dw2, db2)
@@ -287,7 +287,7 @@ def mlp_bwd(dy, x, w1, w2, h, pre):
         dh, _ = _gemm_raw(dy, w2T, True, True, M, K2, N2, N2, N2, 0, 0, 1,
                           epi=4, out_pre=pre)
         db1 = _bias_sum(dh)
-        dw2 = torch.matmul(dy.t(), h)
+        dw2 = matmul(dy.t(), h)      # measured: in-place hand wgrad or library
         db2 = _bias_sum(dy)
         dx, dw1, _ = linear_bwd(dh, x, w1, False, "none", None)
         out["r"] = (dx, dw1, db1, dw2, db2)
@@ -335,6 +335,34 @@ def linear_bwd(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor,
     dy = dy.contiguous()
     M, N = dy.shape
     K = w.shape[1]
+
+    # wgrad dW[N,K] = dy^T[N,M] @ x[M,K] has both operands k-outer (the
+    # contraction index M is the slow dimension of dy and of x). Where the
+    # plan gives such a call the 256 kernel, it reads dy and x in place: no
+    # activation transpose, and dgrad and wgrad each take the backend that
+    # measured faster for them (inside a graph capture both stay hand).
+    if x.stride(-1) == 1 and \
+            ext.gemm_plan(N, K, M, N, x.stride(0), False, False, 0, 1)[0] == 256:
+        if act == "gelu":
+            dyl = torch.empty_like(dy)
+            ext.gelu_bwd(dy.data_ptr(), pre_act.data_ptr(), dyl.data_ptr(),
+                         dy.numel(), _stream())
+        else:
+            dyl = dy
+
+        def _dx_hip():
+            wT = transpose2d(w)    # [K, N]: the weight, a few microseconds
+            return _gemm_raw(dyl, wT, True, True, M, K, N, N, N, 0, 0, 1)[0]
+
+        def _dw_hip():
+            return _gemm_raw(dyl, x, False, False, N, K, M, N, x.stride(0),
+                             0, 0, 1)[0]
+
+        dx = _pick_backend(("lin_bx", M, N, K), _dx_hip,
+                           lambda: torch.matmul(dyl, w))()
+        dw = _pick_backend(("lin_bw", M, N, K), _dw_hip,
+                           lambda: torch.matmul(dyl.t(), x))()
+        return dx, dw, _bias_sum(dyl) if has_bias else None
 
     def _hip():
         # canonicalize to KC x KC: one tuned GEMM schedule serves every
@@ -438,7 +466,10 @@ def _matmul_hip(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     # canonicalize big single GEMMs to KC x KC (unlocks the 256x256
     # deep-pipelined kernel; the transpose is memory-bound and cheap)
     if batch == 1 and M % 256 == 0 and N % 256 == 0 and K % 64 == 0 \
-            and K >= 512:
+            and K >= 512 and not (
+                # two k-outer operands run on the 256 kernel as they lie
+                not a_kc and not b_kc and ext.gemm_plan(
+                    M, N, K, lda, ldb, False, False, 0, 1)[0] == 256):
         if not a_kc:
             a = transpose2d(a.reshape(K, M)).reshape(1, M, K)
             a_kc, lda = True, K
