@@ -158,13 +158,163 @@ def run_shape(B, H, D, S_max, positions, sweep):
         }), flush=True)
 
 
+# -- grouped-query attention + RoPE (Llama decode) --------------------------
+#
+# Three contenders on the same packed projection [q (H D) | k | v (Hkv D)]:
+#   fused    one ops.decode_attention(..., rope_theta) on [B,Hkv,S_max,D]
+#            caches: rope of q and k_new, append, attention, K/V rows read
+#            once per group;
+#   composed the engine's composed GQA step: rope_at x2, index_copy_ x2,
+#            [B,Hkv,G,D] @ K^T over the whole S_max cache, mask, fp32
+#            softmax, @ V;
+#   mha      what served GQA before this kernel: ops.rope in a launch of
+#            its own, K/V new rows and caches expanded to H heads, the
+#            G == 1 kernel on them (G times the K/V bytes).
+# needed_kv_bytes counts the Hkv-head rows: the bytes GQA needs.
+
+THETA = 10000.0
+
+
+def make_gqa_case(B, H, Hkv, D, S_max, p, expanded):
+    torch.manual_seed(0)
+    G = H // Hkv
+    kc = [torch.randn(B, Hkv, S_max, D, dtype=BF16, device="cuda")
+          for _ in range(CALLS)]
+    vc = [torch.randn(B, Hkv, S_max, D, dtype=BF16, device="cuda")
+          for _ in range(CALLS)]
+    ke = ve = None
+    if expanded:
+        ke = [t.repeat_interleave(G, dim=1) for t in kc]
+        ve = [t.repeat_interleave(G, dim=1) for t in vc]
+    qkv = torch.randn(B, (H + 2 * Hkv) * D, dtype=BF16, device="cuda")
+    cur_t = torch.full((1,), p, dtype=torch.long, device="cuda")
+    kpos = torch.arange(S_max, device="cuda")
+    return kc, vc, ke, ve, qkv, cur_t, kpos
+
+
+def _views(qkv, B, H, Hkv, D):
+    return (qkv[:, :H * D].view(B, H, D),
+            qkv[:, H * D:(H + Hkv) * D].view(B, Hkv, D),
+            qkv[:, (H + Hkv) * D:].view(B, Hkv, D))
+
+
+def gqa_fused_fn(B, H, Hkv, D, kc, vc, qkv, cur_t, splits=None):
+    q, k, v = _views(qkv, B, H, Hkv, D)
+
+    def f(i):
+        return ops.decode_attention(q, kc[i], vc[i], cur_t, k_new=k,
+                                    v_new=v, splits=splits,
+                                    rope_theta=THETA).reshape(B, H * D)
+    return f
+
+
+def gqa_composed_fn(B, H, Hkv, D, kc, vc, qkv, cur_t, kpos):
+    from tepdist_amd.ops import reference as ref
+    G = H // Hkv
+    scale = 1.0 / math.sqrt(D)
+    dead = (kpos > cur_t)
+    q, k, v = _views(qkv, B, H, Hkv, D)
+
+    def f(i):
+        qr = ref.rope_at(q, cur_t, THETA).view(B, Hkv, G, D)
+        kc[i].index_copy_(2, cur_t, ref.rope_at(k, cur_t, THETA)[:, :, None])
+        vc[i].index_copy_(2, cur_t, v[:, :, None])
+        scores = ops.matmul(qr.contiguous(), kc[i].transpose(-1, -2)) * scale
+        scores = scores.masked_fill(dead, float("-inf"))
+        p = torch.softmax(scores.float(), dim=-1).to(qkv.dtype)
+        return ops.matmul(p, vc[i]).reshape(B, H * D)
+    return f
+
+
+def gqa_mha_fn(B, H, Hkv, D, ke, ve, qkv, cur_t):
+    G = H // Hkv
+    _, _, v = _views(qkv, B, H, Hkv, D)
+
+    def expand(t):      # [B, Hkv, D] -> [B, H, D], head h <- h // G
+        return t[:, :, None].expand(B, Hkv, G, D).reshape(B, H, D)
+
+    def f(i):
+        # ops.rope rotates by token % seq_len, not by the device position:
+        # the same work and launch as a decode step's rope, other angles
+        qk = ops.rope(qkv[:, :(H + Hkv) * D].reshape(B, H + Hkv, D), B,
+                      THETA)
+        return ops.decode_attention(
+            qk[:, :H], ke[i], ve[i], cur_t,
+            k_new=expand(qk[:, H:]), v_new=expand(v)).reshape(B, H * D)
+    return f
+
+
+def run_gqa_shape(B, H, Hkv, D, S_max, positions, sweep=False, mha=True):
+    for p in positions:
+        kc, vc, ke, ve, qkv, cur_t, kpos = make_gqa_case(B, H, Hkv, D,
+                                                         S_max, p, mha)
+        auto = hip.decode_splits(B * Hkv, S_max, H // Hkv)
+        graphs = {}
+        graphs["fused"], of = capture(
+            gqa_fused_fn(B, H, Hkv, D, kc, vc, qkv, cur_t))
+        graphs["composed"], oc = capture(
+            gqa_composed_fn(B, H, Hkv, D, kc, vc, qkv, cur_t, kpos))
+        if mha:
+            graphs["mha"], _ = capture(
+                gqa_mha_fn(B, H, Hkv, D, ke, ve, qkv, cur_t))
+        diff = (of.float() - oc.float()).abs().max().item()
+        r = time_alternating(graphs)
+        nb = needed_bytes(B, Hkv, D, p)
+        bps = nb / (r["fused"][0] * 1e-6)
+        row = {
+            "bench": "decode_attn_gqa", "B": B, "H": H, "Hkv": Hkv,
+            "G": H // Hkv, "D": D, "S_max": S_max, "pos": p,
+            "splits": auto, "needed_kv_bytes": nb,
+            "fused_bytes_per_s": round(bps, 0),
+            "share_of_hbm_peak": round(bps / HBM_PEAK, 3),
+            "max_abs_diff_fused_vs_composed": round(diff, 5),
+        }
+        for k, v in r.items():
+            row[k + "_us"] = round(v[0], 2)
+            row[k + "_us_min_max"] = [round(x, 2) for x in v[1:]]
+        spread = max(r["fused"][2] - r["fused"][1],
+                     r["composed"][2] - r["composed"][1])
+        row["fused_beats_composed_by_more_than_spread"] = \
+            r["composed"][0] - r["fused"][0] > spread
+        print(json.dumps(row), flush=True)
+        if not sweep:
+            continue
+        gs = {s: capture(gqa_fused_fn(B, H, Hkv, D, kc, vc, qkv, cur_t,
+                                      s))[0] for s in (1, 2, 4, 8, 16)}
+        rs = time_alternating(gs)
+        print(json.dumps({
+            "bench": "decode_attn_gqa_splits", "B": B, "H": H, "Hkv": Hkv,
+            "D": D, "S_max": S_max, "pos": p,
+            "fused_us_by_splits": {str(s): round(v[0], 2)
+                                   for s, v in rs.items()},
+        }), flush=True)
+
+
+def main_gqa():
+    run_gqa_shape(32, 32, 8, 64, 640, (512, 639), sweep=True)  # llama-1b-gqa
+    run_gqa_shape(32, 32, 4, 64, 640, (639,), sweep=True)      # G = 8
+    run_gqa_shape(32, 16, 4, 128, 640, (639,), sweep=True)
+    run_gqa_shape(4, 32, 8, 64, 640, (639,), sweep=True)
+    run_gqa_shape(1, 32, 8, 64, 2048, (2047,), sweep=True)
+    # the remaining (D, G) the kernel covers, fused against composed only
+    run_gqa_shape(32, 16, 16, 64, 640, (639,), mha=False)  # G = 1 + rope
+    run_gqa_shape(32, 32, 16, 64, 640, (639,), mha=False)  # G = 2
+    run_gqa_shape(32, 16, 16, 128, 640, (639,), mha=False)
+    run_gqa_shape(32, 16, 8, 128, 640, (639,), mha=False)
+    run_gqa_shape(32, 32, 4, 128, 640, (639,), sweep=True, mha=False)
+
+
 def main():
     assert torch.cuda.is_available(), "bench_decode_attn needs a GPU"
-    run_shape(32, 16, 64, 640, (512, 639), sweep=True)
-    run_shape(32, 8, 128, 640, (639,), sweep=True)
-    # smaller batches: where the split over KV has to fill the chip
-    run_shape(4, 16, 64, 640, (639,), sweep=True)
-    run_shape(1, 16, 64, 2048, (2047,), sweep=True)
+    which = sys.argv[1] if len(sys.argv) > 1 else "all"
+    if which in ("all", "mha"):
+        run_shape(32, 16, 64, 640, (512, 639), sweep=True)
+        run_shape(32, 8, 128, 640, (639,), sweep=True)
+        # smaller batches: where the split over KV has to fill the chip
+        run_shape(4, 16, 64, 640, (639,), sweep=True)
+        run_shape(1, 16, 64, 2048, (2047,), sweep=True)
+    if which in ("all", "gqa"):
+        main_gqa()
 
 
 if __name__ == "__main__":

@@ -84,6 +84,10 @@ def llama_ir(cfg, batch: int, seq: int) -> Graph:
     """Llama-family exporter (models/llama.py): RMSNorm + rotary + SwiGLU
     decoder in the same flattened (B*S, hidden) form as gpt2_ir, so the
     auto-parallel planner and SpmdTransform apply unchanged."""
+    if getattr(cfg, "n_kv_head", None) not in (None, cfg.n_head):
+        raise NotImplementedError(
+            "llama_ir: grouped-query attention (n_kv_head < n_head) is not "
+            "exported")
     g = Graph()
     V, d, H, L = cfg.vocab_size, cfg.n_embd, cfg.n_head, cfg.n_layer
     hd = cfg.ffn_mult * d

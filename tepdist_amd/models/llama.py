@@ -3,11 +3,20 @@ rotary position embedding, SwiGLU MLP, no biases, untied head — exercises
 the wide-head (D=128) flash-attention path and the llama op kernels
 (ops/csrc/llama_ops.hip). Same training surface as models/gpt2.py
 (forward(ids, labels) -> loss) so the Trainer / bench / parallel layers
-apply unchanged."""
+apply unchanged.
+
+Grouped-query attention (LlamaConfig.n_kv_head < n_head): the packed
+projection is [q (H*D) | k (Hkv*D) | v (Hkv*D)]; the training forward
+rotates q and k, expands K/V to H heads at torch level (head h uses K/V
+head h // G, autograd sums the group's gradients) and calls ops.attention
+as for MHA. A flash kernel that reads GQA K/V natively is out of scope;
+the serving path (inference/engine.py) keeps the cache at Hkv heads and
+its decode kernel reads each K/V row once per group."""
 
 from __future__ import annotations
 
 from dataclasses import dataclass
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -30,6 +39,18 @@ class LlamaConfig:
     ffn_mult: int = 2        # intermediate = ffn_mult * n_embd (llama ~2.7)
     rope_theta: float = 10000.0
     rms_eps: float = 1e-6
+    n_kv_head: Optional[int] = None   # K/V heads (GQA); None = n_head
+
+    def __post_init__(self):
+        if self.n_kv_head is not None and (
+                self.n_kv_head < 1 or self.n_head % self.n_kv_head != 0):
+            raise ValueError(
+                f"n_head {self.n_head} must be a multiple of n_kv_head "
+                f"{self.n_kv_head}")
+
+    @property
+    def kv_heads(self) -> int:
+        return self.n_head if self.n_kv_head is None else self.n_kv_head
 
 
 LLAMA_CONFIGS = {
@@ -38,6 +59,10 @@ LLAMA_CONFIGS = {
     "llama-1b": LlamaConfig(name="llama-1b", n_layer=22, n_embd=2048,
                             n_head=16, n_ctx=2048, vocab_size=32000,
                             ffn_mult=3),
+    # TinyLlama-1.1B-like GQA: 32 x 64 query heads over 8 K/V heads (G = 4)
+    "llama-1b-gqa": LlamaConfig(name="llama-1b-gqa", n_layer=22,
+                                n_embd=2048, n_head=32, n_ctx=2048,
+                                vocab_size=32000, ffn_mult=3, n_kv_head=8),
 }
 
 
@@ -53,14 +78,21 @@ class LlamaBlock(nn.Module):
         h = cfg.ffn_mult * d
         tp = env.tp_size
         assert cfg.n_head % tp == 0
+        if cfg.kv_heads != cfg.n_head and tp > 1:
+            raise NotImplementedError(
+                "grouped-query attention (n_kv_head < n_head) is not "
+                "implemented under tensor parallelism")
         self.cfg = cfg
         self.env = env
         self.n_head_local = cfg.n_head // tp
         self.head_dim = d // cfg.n_head
+        self.n_kv_local = cfg.kv_heads // tp
         self.ln1_g = nn.Parameter(torch.ones(d, dtype=dtype))
         self.ln2_g = nn.Parameter(torch.ones(d, dtype=dtype))
         if tp == 1:
-            self.w_qkv = _param(3 * d, d, dtype=dtype)
+            self.w_qkv = _param(
+                (cfg.n_head + 2 * cfg.kv_heads) * self.head_dim, d,
+                dtype=dtype)
             self.w_o = _param(d, d, dtype=dtype)
             self.w_gate = _param(h, d, dtype=dtype)
             self.w_up = _param(h, d, dtype=dtype)
@@ -82,6 +114,8 @@ class LlamaBlock(nn.Module):
         T = qkv.shape[0]
         nh, hd = self.n_head_local, self.head_dim
         dloc = nh * hd
+        if self.n_kv_local != nh:
+            return self._attn_gqa(qkv, seq_len)
         q, k, v = qkv.split(dloc, dim=-1)
         q = ops.rope(q.reshape(T, nh, hd), seq_len, cfg.rope_theta)
         k = ops.rope(k.reshape(T, nh, hd), seq_len, cfg.rope_theta)
@@ -92,6 +126,25 @@ class LlamaBlock(nn.Module):
         o = ops.attention(heads(q), heads(k),
                           heads(v.reshape(T, nh, hd)), causal=True)
         return o.transpose(1, 2).reshape(T, dloc).contiguous()
+
+    def _attn_gqa(self, qkv, seq_len: int):
+        """Hkv < H: K/V expanded to H heads for the MHA flash kernels."""
+        cfg = self.cfg
+        T = qkv.shape[0]
+        nh, nkv, hd = self.n_head_local, self.n_kv_local, self.head_dim
+        q, k, v = qkv.split([nh * hd, nkv * hd, nkv * hd], dim=-1)
+        q = ops.rope(q.reshape(T, nh, hd), seq_len, cfg.rope_theta)
+        k = ops.rope(k.reshape(T, nkv, hd), seq_len, cfg.rope_theta)
+        b = T // seq_len
+
+        def heads(t, n):
+            return t.reshape(b, seq_len, n, hd).transpose(1, 2)
+
+        def expand(t):    # [b, nkv, s, hd] -> [b, nh, s, hd], head h <- h//G
+            return t.repeat_interleave(nh // nkv, dim=1).contiguous()
+        o = ops.attention(heads(q, nh).contiguous(), expand(heads(k, nkv)),
+                          expand(heads(v, nkv)), causal=True)
+        return o.transpose(1, 2).reshape(T, nh * hd).contiguous()
 
     def forward(self, x, seq_len: int):
         cfg = self.cfg
@@ -154,9 +207,14 @@ class Llama(nn.Module):
                 _draw("wte", (V, d), std, dt, seed, 0, r, tp))
             self.head.weight.copy_(
                 _draw("lm_head", (V, d), std, dt, seed, 0, r, tp))
+        Hkv = cfg.kv_heads
         for i, blk in enumerate(self.blocks):
-            qkv = _draw(f"h{i}.w_qkv", (3, H, hd * d), std, dt, seed,
-                        1, r, tp).reshape(3 * (H // tp) * hd, d)
+            if Hkv == H:
+                qkv = _draw(f"h{i}.w_qkv", (3, H, hd * d), std, dt, seed,
+                            1, r, tp).reshape(3 * (H // tp) * hd, d)
+            else:   # tp == 1: rows [q heads | k heads | v heads]
+                qkv = _draw(f"h{i}.w_qkv", (H + 2 * Hkv, hd * d), std, dt,
+                            seed).reshape((H + 2 * Hkv) * hd, d)
             o = _draw(f"h{i}.w_o", (d, d), std, dt, seed, 1, r, tp)
             gate = _draw(f"h{i}.w_gate", (h, d), std, dt, seed, 0, r, tp)
             up = _draw(f"h{i}.w_up", (h, d), std, dt, seed, 0, r, tp)

@@ -59,6 +59,7 @@ def _needs_build() -> bool:
                                           CSRC / "lds_frag.h",
                                           CSRC / "gemm_plan.h",
                                           CSRC / "gemm_tile.h",
+                                          CSRC / "rope_common.h",
                                           Path(__file__)]
     return any(d.stat().st_mtime > so_mtime for d in deps)
 

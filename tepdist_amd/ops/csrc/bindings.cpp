@@ -150,8 +150,9 @@ PYBIND11_MODULE(_tepdist_hip, m) {
   m.def("decode_attention", [](uintptr_t q, uintptr_t k_new, uintptr_t v_new,
                                uintptr_t k_cache, uintptr_t v_cache,
                                uintptr_t pos, int pos_stride, uintptr_t out,
-                               uintptr_t ws, int B, int H, int S_max, int D,
-                               float scale, int splits, int64_t q_bs,
+                               uintptr_t ws, int B, int H, int Hkv,
+                               int S_max, int D, float scale, int splits,
+                               bool rope, float rope_theta, int64_t q_bs,
                                int64_t q_hs, int64_t n_bs, int64_t n_hs,
                                int64_t c_bs, int64_t c_hs, int64_t c_rs,
                                uintptr_t stream) {
@@ -161,8 +162,8 @@ PYBIND11_MODULE(_tepdist_hip, m) {
         reinterpret_cast<void*>(v_cache),
         reinterpret_cast<const int64_t*>(pos), pos_stride,
         reinterpret_cast<void*>(out), reinterpret_cast<float*>(ws), B, H,
-        S_max, D, scale, splits, q_bs, q_hs, n_bs, n_hs, c_bs, c_hs, c_rs,
-        S(stream));
+        Hkv, S_max, D, scale, splits, rope, rope_theta, q_bs, q_hs, n_bs,
+        n_hs, c_bs, c_hs, c_rs, S(stream));
     check_launch();
   });
 

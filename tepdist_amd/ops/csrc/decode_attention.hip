@@ -24,11 +24,23 @@
 // Rows above p are never loaded: out-of-range lanes re-load the last valid
 // row of their split and are switched off by selects on the score and on
 // the probability, so whatever those rows hold (NaN, Inf) has no effect.
+//
+// Grouped-query attention + RoPE (decode_attn_gqa_kernel): caches hold Hkv
+// heads, q holds H = G * Hkv; query head h attends K/V head h / G. One
+// workgroup per (split, KV head, batch row) keeps the G query fragments and
+// G online-softmax states in registers, so each K/V row is loaded once and
+// used G times. With ROPE, q and k_new are rotated in fp32 at the same
+// clamped p that indexes the cache (angles from rope_common.h, shared with
+// the prefill rope_kernel): q stays fp32; k_new is rounded to bf16 once and
+// that value is both attended to and stored, so the cache holds rotated
+// rows. The G == 1, no-rope call keeps the original decode_attn_kernel.
 
+#include <cmath>
 #include <stdexcept>
 
 #include "common.h"
 #include "kernels.h"
+#include "rope_common.h"
 
 namespace tepdist {
 
@@ -241,6 +253,261 @@ void decode_attn_kernel(const bf16_t* __restrict__ q,
   }
 }
 
+DEV_INLINE uint32_t pack2(float lo, float hi) {
+  return (uint32_t)__builtin_bit_cast(unsigned short, f2bf(lo)) |
+         ((uint32_t)__builtin_bit_cast(unsigned short, f2bf(hi)) << 16);
+}
+
+// GQA (+ optional RoPE) variant: same streaming loop, G queries per K/V
+// row. U is the row-group unroll (UNROLL, or less where G queries' state
+// would push the kernel past 256 VGPRs).
+template <int D, int G, bool ROPE, int U>
+__launch_bounds__(NT) __global__
+void decode_attn_gqa_kernel(const bf16_t* __restrict__ q,
+                            const bf16_t* __restrict__ k_new,
+                            const bf16_t* __restrict__ v_new,
+                            bf16_t* k_cache, bf16_t* v_cache,
+                            const int64_t* __restrict__ pos, int pos_stride,
+                            bf16_t* __restrict__ out, float* __restrict__ ws,
+                            int H, int S_max, float scale_log2e,
+                            float neg2_over_d, float ltheta, int64_t q_bs,
+                            int64_t q_hs, int64_t n_bs, int64_t n_hs,
+                            int64_t c_bs, int64_t c_hs, int64_t c_rs) {
+  constexpr int LPR = D / 8;       // lanes per row
+  constexpr int RPW = WAVE / LPR;  // rows per wave-wide load
+  const int split = blockIdx.x, nsplit = gridDim.x;
+  const int hk = blockIdx.y, b = blockIdx.z;  // hk: K/V head
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;
+  const int sub = lane / LPR;
+  const int col = (lane % LPR) * 8;
+  const int pcol = col ^ (D / 2);  // RoPE partner elements (i +- D/2)
+
+  int64_t p64 = pos[(int64_t)b * pos_stride];
+  p64 = p64 < 0 ? 0 : p64;
+  p64 = p64 > S_max - 1 ? S_max - 1 : p64;
+  const int p = (int)p64;
+  const bool append = k_new != nullptr;
+  const int p_new = append ? p : -1;  // logical row served by k_new/v_new
+  const int n_tot = p + 1;
+
+  int L = (n_tot + nsplit - 1) / nsplit;
+  L = (L + RPW - 1) / RPW * RPW;
+  const int r0 = min(split * L, n_tot);
+  const int r1 = min(r0 + L, n_tot);
+  const int ng = (r1 - r0 + RPW - 1) / RPW;
+
+  const bf16_t* kc = k_cache + b * c_bs + hk * c_hs + col;
+  const bf16_t* vc = v_cache + b * c_bs + hk * c_hs + col;
+  const bf16_t* kn = append ? k_new + b * n_bs + hk * n_hs : nullptr;
+  const bf16_t* vn = append ? v_new + b * n_bs + hk * n_hs : nullptr;
+
+  // rotation of this lane's 8 elements: y = x * cs + partner * sn, with
+  // sn negated in the first half of the row (rotate-half)
+  float cs[8], sn[8];
+  if (ROPE) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float s, c;
+      rope_sincos(p, (col + e) & (D / 2 - 1), neg2_over_d, ltheta, &s, &c);
+      cs[e] = c;
+      sn[e] = col < D / 2 ? -s : s;
+    }
+  }
+
+  // G query fragments, fp32, rotated (never rounded), scale*log2e folded in
+  float qf[G][8];
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const bf16_t* qp = q + b * q_bs + (int64_t)(hk * G + g) * q_hs;
+    unpack8(*reinterpret_cast<const uint4*>(qp + col), qf[g]);
+    if (ROPE) {
+      float xp[8];
+      unpack8(*reinterpret_cast<const uint4*>(qp + pcol), xp);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) qf[g][e] = qf[g][e] * cs[e] + xp[e] * sn[e];
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) qf[g][e] *= scale_log2e;
+  }
+
+  // the new K row, rotated and rounded to bf16 once: every lane keeps its
+  // own 8 elements (4 VGPRs) for the attend, lanes [0, LPR) store them
+  // (four scalars, not a uint4: the struct would live in scratch)
+  uint32_t kr0 = 0u, kr1 = 0u, kr2 = 0u, kr3 = 0u;
+  if (ROPE && append) {
+    float x[8], xp[8];
+    unpack8(*reinterpret_cast<const uint4*>(kn + col), x);
+    unpack8(*reinterpret_cast<const uint4*>(kn + pcol), xp);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) x[e] = x[e] * cs[e] + xp[e] * sn[e];
+    kr0 = pack2(x[0], x[1]);
+    kr1 = pack2(x[2], x[3]);
+    kr2 = pack2(x[4], x[5]);
+    kr3 = pack2(x[6], x[7]);
+  }
+
+  if (append && split == 0 && wid == 0 && lane < 2 * LPR) {
+    // lanes [0, LPR) store K, [LPR, 2*LPR) store V: one 16-B vector
+    // store each into cache row p (a row nobody in this launch reads)
+    const bool is_v = lane >= LPR;
+    bf16_t* base = is_v ? v_cache : k_cache;
+    uint4 val = *reinterpret_cast<const uint4*>((is_v ? vn : kn) + col);
+    if (ROPE && !is_v) val = make_uint4(kr0, kr1, kr2, kr3);
+    *reinterpret_cast<uint4*>(base + b * c_bs + hk * c_hs +
+                              (int64_t)p * c_rs + col) = val;
+  }
+
+  float m[G], l[G], acc[G][8];
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    m[g] = NEG;
+    l[g] = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[g][e] = 0.f;
+  }
+
+  auto load = [&](int g0, uint4 (&kk)[U], uint4 (&vv)[U]) {
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      const int r = r0 + (g0 + NW * j) * RPW + sub;
+      const int rc = r < r1 ? r : r1 - 1;  // r1 > r0 >= 0 when called
+      const bool nw = rc == p_new;
+      const bf16_t* kp = nw ? kn + col : kc + (int64_t)rc * c_rs;
+      const bf16_t* vp = nw ? vn + col : vc + (int64_t)rc * c_rs;
+      kk[j] = *reinterpret_cast<const uint4*>(kp);
+      vv[j] = *reinterpret_cast<const uint4*>(vp);
+    }
+  };
+  auto consume = [&](int g0, const uint4 (&kk)[U], const uint4 (&vv)[U]) {
+    float s[G][U];
+    bool ok[U];
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      const int r = r0 + (g0 + NW * j) * RPW + sub;
+      ok[j] = r < r1;
+      uint4 ku = kk[j];
+      if (ROPE) {  // the new row is attended in its rotated form
+        const bool nw = r == p_new;
+        ku.x = nw ? kr0 : ku.x;
+        ku.y = nw ? kr1 : ku.y;
+        ku.z = nw ? kr2 : ku.z;
+        ku.w = nw ? kr3 : ku.w;
+      }
+      float kf[8];
+      unpack8(ku, kf);
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        float dot = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dot += qf[g][e] * kf[e];
+#pragma unroll
+        for (int off = LPR / 2; off > 0; off >>= 1)
+          dot += __shfl_xor(dot, off, 64);
+        s[g][j] = ok[j] ? dot : NEG;
+      }
+    }
+    float m_new[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      m_new[g] = m[g];
+#pragma unroll
+      for (int j = 0; j < U; ++j) m_new[g] = fmaxf(m_new[g], s[g][j]);
+      const float alpha = ex2(m[g] - m_new[g]);
+      l[g] *= alpha;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[g][e] *= alpha;
+      m[g] = m_new[g];
+    }
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      float vf[8];
+      unpack8(vv[j], vf);
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        const float pj = ok[j] ? ex2(s[g][j] - m_new[g]) : 0.f;
+        l[g] += pj;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[g][e] += pj * vf[e];
+      }
+    }
+  };
+
+  // ping-pong over two register sets with an unconditional clamped
+  // look-ahead load, as in decode_attn_kernel
+  constexpr int STEP = NW * U;
+  if (ng > 0) {
+    uint4 ka[U], va[U], kb[U], vb[U];
+    int g0 = wid;
+    load(g0, ka, va);
+    while (g0 < ng) {
+      load(g0 + STEP, kb, vb);
+      consume(g0, ka, va);
+      g0 += STEP;
+      if (g0 >= ng) break;
+      load(g0 + STEP, ka, va);
+      consume(g0, kb, vb);
+      g0 += STEP;
+    }
+  }
+
+  // merge the RPW lane groups of the wave, per group member
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+#pragma unroll
+    for (int off = LPR; off < WAVE; off <<= 1) {
+      const float m_o = __shfl_xor(m[g], off, 64);
+      const float l_o = __shfl_xor(l[g], off, 64);
+      const float mm = fmaxf(m[g], m_o);
+      const float a = ex2(m[g] - mm), c = ex2(m_o - mm);
+      l[g] = l[g] * a + l_o * c;
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        acc[g][e] = acc[g][e] * a + __shfl_xor(acc[g][e], off, 64) * c;
+      m[g] = mm;
+    }
+  }
+
+  // merge the block's waves through LDS
+  __shared__ float sm_m[G][NW], sm_l[G][NW], sm_acc[G][NW][D];
+  if (lane < LPR) {
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) sm_acc[g][wid][col + e] = acc[g][e];
+      if (lane == 0) {
+        sm_m[g][wid] = m[g];
+        sm_l[g][wid] = l[g];
+      }
+    }
+  }
+  __syncthreads();
+  for (int idx = threadIdx.x; idx < G * D; idx += NT) {
+    const int g = idx / D, t = idx % D;
+    float mm = sm_m[g][0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) mm = fmaxf(mm, sm_m[g][w]);
+    float lt = 0.f, at = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      const float c = ex2(sm_m[g][w] - mm);
+      lt += c * sm_l[g][w];
+      at += c * sm_acc[g][w][t];
+    }
+    const int64_t bh = (int64_t)b * H + hk * G + g;  // query head
+    if (nsplit == 1) {
+      out[bh * D + t] = f2bf(at / lt);
+    } else {
+      float* w = ws + (bh * nsplit + split) * (D + 2);
+      if (t == 0) {
+        w[0] = mm;
+        w[1] = lt;
+      }
+      w[2 + t] = at;
+    }
+  }
+}
+
 // log-sum-exp combine of the per-split partials; one block of D threads
 // per (b, h).
 template <int D>
@@ -270,8 +537,9 @@ bool aligned16(const void* p) {
 void decode_attention_bf16(const void* q, const void* k_new,
                            const void* v_new, void* k_cache, void* v_cache,
                            const int64_t* pos, int pos_stride, void* out,
-                           float* ws, int B, int H, int S_max, int D,
-                           float scale, int splits, int64_t q_bs,
+                           float* ws, int B, int H, int Hkv, int S_max,
+                           int D, float scale, int splits, bool rope,
+                           float rope_theta, int64_t q_bs,
                            int64_t q_hs, int64_t n_bs, int64_t n_hs,
                            int64_t c_bs, int64_t c_hs, int64_t c_rs,
                            hipStream_t stream) {
@@ -281,6 +549,14 @@ void decode_attention_bf16(const void* q, const void* k_new,
     throw std::runtime_error("decode_attention: splits must be in [1, 32]");
   if (B < 1 || B > 65535 || H < 1 || H > 65535 || S_max < 1)
     throw std::runtime_error("decode_attention: bad B/H/S_max");
+  if (Hkv < 1 || H % Hkv != 0)
+    throw std::runtime_error("decode_attention: H must be a multiple of Hkv");
+  const int G = H / Hkv;
+  if (G != 1 && G != 2 && G != 4 && G != 8)
+    throw std::runtime_error("decode_attention: group size H/Hkv must be "
+                             "1, 2, 4 or 8");
+  if (rope && !(rope_theta > 0.f))
+    throw std::runtime_error("decode_attention: rope_theta must be > 0");
   if (pos_stride != 0 && pos_stride != 1)
     throw std::runtime_error("decode_attention: pos_stride must be 0 or 1");
   if ((k_new == nullptr) != (v_new == nullptr))
@@ -298,7 +574,7 @@ void decode_attention_bf16(const void* q, const void* k_new,
   if (c_rs < D)
     throw std::runtime_error("decode_attention: cache row stride < D");
 
-  const dim3 grid(splits, H, B), blk(NT);
+  const dim3 grid(splits, Hkv, B), blk(NT);
   const float sl = scale * LOG2E;
   const bf16_t* qp = static_cast<const bf16_t*>(q);
   const bf16_t* knp = static_cast<const bf16_t*>(k_new);
@@ -316,8 +592,43 @@ void decode_attention_bf16(const void* q, const void* k_new,
       hipLaunchKernelGGL(decode_attn_combine_kernel<DD>, dim3(B * H),       \
                          dim3(DD), 0, stream, ws, op, splits);              \
   } while (0)
-  if (D == 64) DA_LAUNCH(64); else DA_LAUNCH(128);
+  if (G == 1 && !rope) {
+    if (D == 64) DA_LAUNCH(64); else DA_LAUNCH(128);
+    return;
+  }
 #undef DA_LAUNCH
+  const float ltheta = rope ? logf(rope_theta) : 0.f;
+  const float neg2 = -2.0f / D;
+  // G = 8 halves the unroll: 8 queries' state plus two 4-deep load sets
+  // would not fit 256 VGPRs (two waves per SIMD)
+#define DG_LAUNCH(DD, GG, RR)                                               \
+  do {                                                                      \
+    hipLaunchKernelGGL(                                                     \
+        (decode_attn_gqa_kernel<DD, GG, RR, (GG == 8 ? UNROLL / 2 : UNROLL)>), \
+        grid, blk, 0, stream, qp, knp, vnp, kcp, vcp, pos, pos_stride, op,  \
+        ws, H, S_max, sl, neg2, ltheta, q_bs, q_hs, n_bs, n_hs, c_bs, c_hs, \
+        c_rs);                                                              \
+    if (splits > 1)                                                         \
+      hipLaunchKernelGGL(decode_attn_combine_kernel<DD>, dim3(B * H),       \
+                         dim3(DD), 0, stream, ws, op, splits);              \
+  } while (0)
+#define DG_ROPE(DD, GG)                                                     \
+  do {                                                                      \
+    if (rope) DG_LAUNCH(DD, GG, true); else DG_LAUNCH(DD, GG, false);       \
+  } while (0)
+#define DG_GROUP(DD)                                                        \
+  do {                                                                      \
+    switch (G) {                                                            \
+      case 1: DG_LAUNCH(DD, 1, true); break; /* G == 1 gets here with rope */ \
+      case 2: DG_ROPE(DD, 2); break;                                        \
+      case 4: DG_ROPE(DD, 4); break;                                        \
+      default: DG_ROPE(DD, 8); break;                                       \
+    }                                                                       \
+  } while (0)
+  if (D == 64) DG_GROUP(64); else DG_GROUP(128);
+#undef DG_GROUP
+#undef DG_ROPE
+#undef DG_LAUNCH
 }
 
 }  // namespace tepdist

@@ -106,11 +106,18 @@ void attention_bwd_bf16(const void* q, const void* k, const void* v,
 // is never read by that launch). out: [B,H,D] bf16 contiguous. ws: fp32
 // [B*H*splits*(D+2)], only read when splits > 1. D in {64,128},
 // splits in [1,32]; anything else throws.
+// Grouped-query attention: the caches and k_new/v_new hold Hkv heads, q and
+// out hold H = G*Hkv with G in {1,2,4,8}; query head h attends K/V head
+// h / G. With rope, q and k_new are rotated (rotate-half, theta =
+// rope_theta) by the clamped position p inside the kernel: q in fp32,
+// k_new rounded to bf16 once, attended to and stored in that form (the
+// cache holds rotated rows); v_new is stored as is.
 void decode_attention_bf16(const void* q, const void* k_new,
                            const void* v_new, void* k_cache, void* v_cache,
                            const int64_t* pos, int pos_stride, void* out,
-                           float* ws, int B, int H, int S_max, int D,
-                           float scale, int splits, int64_t q_bs,
+                           float* ws, int B, int H, int Hkv, int S_max,
+                           int D, float scale, int splits, bool rope,
+                           float rope_theta, int64_t q_bs,
                            int64_t q_hs, int64_t n_bs, int64_t n_hs,
                            int64_t c_bs, int64_t c_hs, int64_t c_rs,
                            hipStream_t stream);

@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "rope_common.h"
 
 namespace tepdist {
 
@@ -205,9 +206,8 @@ void rope_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y,
     const int64_t th = i / (D / 2);
     const int64_t tok = th / heads;
     const int pos = (int)(tok % seq_len);
-    const float freq = __expf(ltheta * neg2_over_d * d);
     float sn, cs;
-    __sincosf(pos * freq, &sn, &cs);
+    rope_sincos(pos, d, neg2_over_d, ltheta, &sn, &cs);
     if (BWD) sn = -sn;
     const int64_t base = th * D + d;
     const float x1 = bf2f(x[base]);

@@ -646,20 +646,29 @@ def attention_bwd(dout: torch.Tensor, q, k, v, residuals,
 _DECODE_SPLITS = os.environ.get("TEPDIST_DECODE_SPLITS")
 
 
-def decode_splits(bh: int, s_max: int) -> int:
-    """KV splits for decode_attention: a static function of (B*H, S_max)
-    only (no device read, so a captured launch keeps its grid). Measured
+def decode_splits(bh: int, s_max: int, group: int = 1) -> int:
+    """KV splits for decode_attention: a static function of the shapes
+    (bh = B*Hkv workgroups per split, S_max, group = H/Hkv) only (no
+    device read, so a captured launch keeps its grid). Measured
     (docs/KERNELS.md "Decode attention", profiles/decode_attention.json):
     the combine launch costs 2-3 us, so at S_max 640 one workgroup per
     (b, h) wins from B*H = 64 up (6.8 vs 8.1 us at 64, 17.8 vs 20.5 us at
     512); splitting pays only when few (b, h) pairs stream a long cache
     (B*H = 16, S_max 2048: 14.3 us unsplit, 9.4 us at 4 splits, 10.1 at
     8). Hence: double while the grid stays within 64 workgroups and each
-    split keeps >= 512 rows. TEPDIST_DECODE_SPLITS pins a value."""
+    split keeps >= 512 rows. With group >= 4 a workgroup serves 4-8
+    queries in 180-244 VGPRs (two waves per SIMD), there are 1/group as
+    many workgroups and each takes longer, so filling the 256 CUs pays
+    earlier (profiles/decode_attention_gqa.json: B*Hkv = 128, S_max 640,
+    G = 8, D = 64: 26.2 us unsplit, 21.0 at 2, 22.6 at 4; B*Hkv = 256,
+    G = 4: 15.1 unsplit, 19.7 at 2): double while the grid stays within
+    256 workgroups and each split keeps >= 256 rows.
+    TEPDIST_DECODE_SPLITS pins a value."""
     if _DECODE_SPLITS:
         return max(1, min(32, int(_DECODE_SPLITS)))
+    max_wg, min_rows = (256, 256) if group >= 4 else (64, 512)
     s = 1
-    while s < 16 and bh * s * 2 <= 64 and s_max // (s * 2) >= 512:
+    while s < 16 and bh * s * 2 <= max_wg and s_max // (s * 2) >= min_rows:
         s *= 2
     return s
 
@@ -669,34 +678,46 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
                      k_new: Optional[torch.Tensor] = None,
                      v_new: Optional[torch.Tensor] = None,
                      scale: Optional[float] = None,
-                     splits: Optional[int] = None) -> torch.Tensor:
+                     splits: Optional[int] = None,
+                     rope_theta: Optional[float] = None) -> torch.Tensor:
     """Fused single-query attention over a KV cache (decode_attention.hip).
     Same semantics as reference.decode_attention, including the in-place
-    cache write of (k_new, v_new) at the device-side position. Strided
-    [B, H, D] views (e.g. of the packed qkv projection) and cache slices
-    are consumed without a copy."""
+    cache write of (k_new, v_new) at the device-side position, grouped
+    queries (caches and new rows with Hkv heads, H / Hkv in {1, 2, 4, 8})
+    and the in-kernel rotation of q and k_new when rope_theta is given.
+    Strided [B, H, D] views (e.g. of the packed qkv projection) and cache
+    slices are consumed without a copy."""
+    if q.dim() != 3 or k_cache.dim() != 4:
+        raise ValueError("decode_attention: q [B,H,D], caches "
+                         "[B,Hkv,S_max,D]")
     B, H, D = q.shape
-    S_max = k_cache.shape[2]
+    Hkv, S_max = k_cache.shape[1], k_cache.shape[2]
     if q.dtype != BF16 or k_cache.dtype != BF16 or v_cache.dtype != BF16:
         raise ValueError("decode_attention: hip backend is bf16-only")
     if D not in (64, 128):
         raise ValueError(f"decode_attention: head dim {D} not in (64, 128)")
     if (k_new is None) != (v_new is None):
         raise ValueError("decode_attention: k_new and v_new go together")
-    if tuple(k_cache.shape) != (B, H, S_max, D) or \
+    if Hkv < 1 or H % Hkv != 0 or H // Hkv not in (1, 2, 4, 8):
+        raise ValueError(f"decode_attention: {H} query heads over {Hkv} "
+                         "K/V heads: the group size must be 1, 2, 4 or 8")
+    if tuple(k_cache.shape) != (B, Hkv, S_max, D) or \
             v_cache.shape != k_cache.shape or \
             v_cache.stride() != k_cache.stride():
         raise ValueError("decode_attention: k_cache/v_cache must be "
-                         "[B,H,S_max,D] with equal strides")
+                         "[B,Hkv,S_max,D] with equal strides")
     if q.stride(2) != 1 or k_cache.stride(3) != 1:
         raise ValueError("decode_attention: D must be contiguous")
+    if rope_theta is not None and not rope_theta > 0:
+        raise ValueError("decode_attention: rope_theta must be positive")
     n_bs = n_hs = 0
     if k_new is not None:
         if k_new.dtype != BF16 or v_new.dtype != BF16 or \
-                k_new.shape != q.shape or v_new.shape != q.shape or \
+                tuple(k_new.shape) != (B, Hkv, D) or \
+                v_new.shape != k_new.shape or \
                 k_new.stride() != v_new.stride() or k_new.stride(2) != 1:
             raise ValueError("decode_attention: k_new/v_new must be bf16 "
-                             "[B,H,D] with equal strides, D contiguous")
+                             "[B,Hkv,D] with equal strides, D contiguous")
         n_bs, n_hs = k_new.stride(0), k_new.stride(1)
     pos = positions.reshape(-1)
     if pos.dtype != torch.int64 or not pos.is_cuda or \
@@ -708,14 +729,16 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
     if scale is None:
         scale = 1.0 / math.sqrt(D)
     if splits is None:
-        splits = decode_splits(B * H, S_max)
+        splits = decode_splits(B * Hkv, S_max, H // Hkv)
     out = torch.empty(B, H, D, dtype=BF16, device=q.device)
     ws = torch.empty(B * H * splits * (D + 2), dtype=torch.float32,
                      device=q.device) if splits > 1 else None
     ext.decode_attention(q.data_ptr(), _p(k_new), _p(v_new),
                          k_cache.data_ptr(), v_cache.data_ptr(),
                          pos.data_ptr(), pos_stride, out.data_ptr(), _p(ws),
-                         B, H, S_max, D, scale, splits, q.stride(0),
+                         B, H, Hkv, S_max, D, scale, splits,
+                         rope_theta is not None, float(rope_theta or 0.0),
+                         q.stride(0),
                          q.stride(1), n_bs, n_hs, k_cache.stride(0),
                          k_cache.stride(1), k_cache.stride(2), _stream())
     return out

@@ -272,22 +272,28 @@ def attention_qkv(qkv, heads: int, causal: bool = True):
 
 def decode_attention(q, k_cache, v_cache, positions, k_new=None, v_new=None,
                      scale: Optional[float] = None,
-                     splits: Optional[int] = None):
+                     splits: Optional[int] = None,
+                     rope_theta: Optional[float] = None):
     """Single-query attention over a KV cache (inference only, no
-    autograd). q/k_new/v_new [B, H, D], caches [B, H, S_max, D],
-    positions int64 [1] or [B] on the tensors' device. With (k_new, v_new)
-    the new row is written in place into cache[b, :, positions[b]] and
-    attended to; otherwise cache rows 0..positions[b] are attended.
-    `splits` (GPU only) pins the KV split count; None = host heuristic."""
+    autograd). q [B, H, D], k_new/v_new [B, Hkv, D], caches
+    [B, Hkv, S_max, D], positions int64 [1] or [B] on the tensors' device.
+    Hkv < H is grouped-query attention: query head h attends K/V head
+    h // (H // Hkv). With (k_new, v_new) the new row is written in place
+    into cache[b, :, positions[b]] and attended to; otherwise cache rows
+    0..positions[b] are attended. With `rope_theta`, q and k_new are
+    rotated (rotate-half, as ops.rope) by the clamped position first: q in
+    fp32 without rounding, k_new rounded once to the cache dtype, so the
+    cache holds rotated rows. `splits` (GPU only) pins the KV split count;
+    None = host heuristic."""
     for t in (q, k_cache, v_cache, k_new, v_new):
         assert t is None or not t.requires_grad, \
             "decode_attention has no backward"
     be = _backend(q)
     if be is ref:
         return ref.decode_attention(q, k_cache, v_cache, positions, k_new,
-                                    v_new, scale)
+                                    v_new, scale, rope_theta)
     return be.decode_attention(q, k_cache, v_cache, positions, k_new, v_new,
-                               scale, splits)
+                               scale, splits, rope_theta)
 
 
 # --------------------------------------------------------------------------

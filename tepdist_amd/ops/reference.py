@@ -196,31 +196,48 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
                      v_cache: torch.Tensor, positions: torch.Tensor,
                      k_new: Optional[torch.Tensor] = None,
                      v_new: Optional[torch.Tensor] = None,
-                     scale: Optional[float] = None) -> torch.Tensor:
-    """Single-query attention over a KV cache. q/k_new/v_new: [B, H, D];
-    k_cache/v_cache: [B, H, S_max, D]; positions: int64 [1] or [B], clamped
-    into [0, S_max-1]. With (k_new, v_new) the new row is first written
+                     scale: Optional[float] = None,
+                     rope_theta: Optional[float] = None) -> torch.Tensor:
+    """Single-query attention over a KV cache. q: [B, H, D]; k_new/v_new:
+    [B, Hkv, D]; k_cache/v_cache: [B, Hkv, S_max, D] with H a multiple of
+    Hkv (grouped-query attention: query head h attends K/V head
+    h // (H // Hkv)); positions: int64 [1] or [B], clamped into
+    [0, S_max-1]. With (k_new, v_new) the new row is first written
     IN PLACE into cache[b, :, p[b]]; batch row b then attends cache rows
     0..p[b] inclusive. Rows above p[b] have no influence whatever they hold
-    (NaN included). fp32 math, returns [B, H, D] in q.dtype."""
+    (NaN included). With rope_theta, q and k_new are first rotated by p[b]
+    in fp32 (rope_at's convention): q is used unrounded, the rotated k_new
+    is cast to the cache dtype when written, so the cache holds rotated
+    rows; without k_new only q is rotated. fp32 math, returns [B, H, D] in
+    q.dtype."""
     assert (k_new is None) == (v_new is None)
     B, H, D = q.shape
-    S_max = k_cache.shape[2]
+    Hkv, S_max = k_cache.shape[1], k_cache.shape[2]
+    assert H % Hkv == 0, (H, Hkv)
+    G = H // Hkv
     if scale is None:
         scale = 1.0 / math.sqrt(D)
     pos = positions.reshape(-1).long().clamp(0, S_max - 1)
     assert pos.numel() in (1, B), positions.shape
     pos = pos.expand(B)
+    qf = q.float()
+    if rope_theta is not None:
+        qf = _rope_at_f32(qf, pos[:, None], rope_theta)
     if k_new is not None:
+        assert k_new.shape == (B, Hkv, D) and v_new.shape == k_new.shape
+        if rope_theta is not None:
+            k_new = _rope_at_f32(k_new, pos[:, None], rope_theta)
         bidx = torch.arange(B, device=q.device)
         k_cache[bidx, :, pos] = k_new.to(k_cache.dtype)
         v_cache[bidx, :, pos] = v_new.to(v_cache.dtype)
     dead = torch.arange(S_max, device=q.device)[None, :] > pos[:, None]
-    scores = torch.einsum("bhd,bhsd->bhs", q.float(), k_cache.float()) * scale
-    scores = scores.masked_fill(dead[:, None, :], float("-inf"))
+    scores = torch.einsum("bhgd,bhsd->bhgs", qf.reshape(B, Hkv, G, D),
+                          k_cache.float()) * scale
+    scores = scores.masked_fill(dead[:, None, None, :], float("-inf"))
     p = torch.softmax(scores, dim=-1)
     v32 = v_cache.float().masked_fill(dead[:, None, :, None], 0.0)
-    return torch.einsum("bhs,bhsd->bhd", p, v32).to(q.dtype)
+    return torch.einsum("bhgs,bhsd->bhgd", p, v32).reshape(B, H, D) \
+        .to(q.dtype)
 
 
 # --------------------------------------------------------------------------
@@ -356,6 +373,27 @@ def rope_fwd(x: torch.Tensor, seq_len: int, theta: float = 10000.0):
     x1, x2 = xf[..., :D // 2], xf[..., D // 2:]
     y = torch.cat([x1 * cos - x2 * sin, x2 * cos + x1 * sin], dim=-1)
     return y.to(x.dtype)
+
+
+def _rope_at_f32(x: torch.Tensor, positions: torch.Tensor, theta: float):
+    D = x.shape[-1]
+    i = torch.arange(D // 2, device=x.device).float()
+    freq = theta ** (-2.0 * i / D)
+    ang = positions.to(x.device)[..., None].float() * freq
+    cos, sin = ang.cos(), ang.sin()
+    xf = x.float()
+    x1, x2 = xf[..., :D // 2], xf[..., D // 2:]
+    return torch.cat([x1 * cos - x2 * sin, x2 * cos + x1 * sin], dim=-1)
+
+
+def rope_at(x: torch.Tensor, positions: torch.Tensor,
+            theta: float = 10000.0):
+    """rope_fwd's rotation at explicit positions: x [..., D], positions an
+    integer tensor broadcast over x's leading dims (e.g. [T, 1] against
+    [B, T, H, D]). Torch ops on the tensors' device only, no host sync, so
+    it runs inside a captured decode step with the position on the
+    device."""
+    return _rope_at_f32(x, positions, theta).to(x.dtype)
 
 
 def rope_bwd(dy: torch.Tensor, seq_len: int, theta: float = 10000.0):
