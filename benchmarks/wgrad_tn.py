@@ -13,6 +13,15 @@ events; the windows of a, b, c are interleaved in one process. Reports the
 per-call median and min..max over the windows in microseconds.
 
 Run on the GPU: python benchmarks/wgrad_tn.py [--out profiles/wgrad_tn.json]
+
+--colsum times the bias gradient instead, same shapes and method:
+
+  d  b, then the streaming bias sum over dy (hip._bias_sum: workspace
+     fill, bias_sum kernel, cast), what a biased site ran before
+  e  one hand call that also returns the column sums of dy (colsum_out)
+  b  the in-place wgrad alone, to show what the column sums add to it
+
+python benchmarks/wgrad_tn.py --colsum [--out profiles/wgrad_colsum.json]
 """
 import argparse
 import json
@@ -49,6 +58,17 @@ def library(dy, x, N, K):
     return torch.matmul(dy.t(), x)
 
 
+def in_place_plus_bias_sum(dy, x, N, K):
+    return in_place(dy, x, N, K), hip._bias_sum(dy)
+
+
+def fused_colsum(dy, x, N, K):
+    db = torch.empty(N, dtype=BF16, device=dy.device)
+    dw = hip._gemm_raw(dy, x, False, False, N, K, M, N, K, 0, 0, 1,
+                       colsum_out=db)[0]
+    return dw, db
+
+
 def window(fn, sets, N, K):
     """Microseconds per call over one pass through the operand sets."""
     beg = torch.cuda.Event(enable_timing=True)
@@ -64,10 +84,14 @@ def window(fn, sets, N, K):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--colsum", action="store_true")
     args = ap.parse_args()
     torch.manual_seed(0)
     ways = [("a_transposes_plus_kc_gemm", with_transposes),
             ("b_in_place", in_place), ("c_torch_matmul", library)]
+    if args.colsum:
+        ways = [("d_in_place_plus_bias_sum", in_place_plus_bias_sum),
+                ("e_fused_colsum", fused_colsum), ("b_in_place", in_place)]
     rows = []
     for name, N, K in SHAPES:
         plan = hip.ext.gemm_plan(N, K, M, N, K, False, False, 0, 1)[:3]
@@ -77,7 +101,15 @@ def main():
                 for _ in range(SETS)]
         # the three agree before anything is timed
         ref = library(*sets[0], N, K).float()
-        for _, fn in ways[:2]:
+        if args.colsum:
+            dw_d, db_d = in_place_plus_bias_sum(*sets[0], N, K)
+            dw_e, db_e = fused_colsum(*sets[0], N, K)
+            assert torch.equal(dw_d, dw_e), name
+            s32 = sets[0][0].float().sum(0)
+            for db in (db_d, db_e):
+                err = (db.float() - s32).abs().max().item()
+                assert err < 3e-2 * M ** 0.5, (name, err)
+        for _, fn in ([] if args.colsum else ways[:2]):
             err = (fn(*sets[0], N, K).float() - ref).abs().max().item()
             assert err < 3e-2 * M ** 0.5, (name, err)
         times = {w: [] for w, _ in ways}

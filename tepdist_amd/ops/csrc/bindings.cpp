@@ -7,6 +7,9 @@
 
 #include <hip/hip_runtime.h>
 
+#include <stdexcept>
+#include <string>
+
 #include "common.h"
 #include "gemm_plan.h"
 #include "kernels.h"
@@ -29,14 +32,33 @@ PYBIND11_MODULE(_tepdist_hip, m) {
                    uintptr_t bias, int M, int N, int K, int lda, int ldb,
                    int ldc, int64_t sa, int64_t sb, int64_t sc, int batch,
                    bool a_kc, bool b_kc, int epi, uintptr_t splitk_ws,
-                   uintptr_t stream) {
+                   uintptr_t stream, uintptr_t colsum_out) {
     gemm_bf16(reinterpret_cast<void*>(A), reinterpret_cast<void*>(B),
               reinterpret_cast<void*>(C), reinterpret_cast<void*>(Cpre),
               reinterpret_cast<void*>(bias), M, N, K, lda, ldb, ldc, sa, sb,
               sc, batch, a_kc, b_kc, epi, reinterpret_cast<float*>(splitk_ws),
-              S(stream));
+              reinterpret_cast<void*>(colsum_out), S(stream));
     check_launch();
-  });
+  }, py::arg("A"), py::arg("B"), py::arg("C"), py::arg("Cpre"),
+     py::arg("bias"), py::arg("M"), py::arg("N"), py::arg("K"),
+     py::arg("lda"), py::arg("ldb"), py::arg("ldc"), py::arg("sa"),
+     py::arg("sb"), py::arg("sc"), py::arg("batch"), py::arg("a_kc"),
+     py::arg("b_kc"), py::arg("epi"), py::arg("splitk_ws"),
+     py::arg("stream"), py::arg("colsum_out") = 0);
+
+  // fp32 workspace floats of the same call's plan (0 = none needed); with
+  // colsum it throws where the plan cannot give column sums. Host-only.
+  m.def("gemm_ws_floats", [](int M, int N, int K, int lda, int ldb,
+                             bool a_kc, bool b_kc, int epi, int batch,
+                             bool colsum) {
+    const GemmPlan p = gemm_plan(M, N, K, lda, ldb, a_kc, b_kc, epi, batch);
+    if (colsum)
+      if (const char* why = colsum_why_not(p, a_kc, b_kc, batch))
+        throw std::runtime_error(std::string("gemm_ws_floats: ") + why);
+    return gemm_ws_floats(p, M, N, colsum);
+  }, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("lda"),
+     py::arg("ldb"), py::arg("a_kc") = true, py::arg("b_kc") = true,
+     py::arg("epi") = 0, py::arg("batch") = 1, py::arg("colsum") = false);
 
   // (kernel, split_k, k_chunk, why_not) — host-only, needs no GPU
   m.def("gemm_plan", [](int M, int N, int K, int lda, int ldb, bool a_kc,

@@ -315,11 +315,60 @@ void gemm_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B,
   }
 }
 
+// Column sums from the parts the 256 kernel's CS variant wrote (nparts
+// vectors of m floats). Block `blk` owns CS_COLS columns; its CS_GROUPS
+// thread groups each add every CS_GROUPS-th part in index order (up to 128
+// parts per column at the flagship shapes: one thread per column would
+// chain that many dependent loads), then group 0 adds the group sums in
+// group order and rounds to bf16 once. All fp32, a fixed order, no
+// atomics: the same bits on every call.
+constexpr int CS_COLS = 32, CS_GROUPS = NTHREADS / CS_COLS;
+
+DEV_INLINE void colsum_reduce(const float* __restrict__ parts,
+                              bf16_t* __restrict__ out, int nparts, int m,
+                              int blk, float* sh) {
+  const int c = threadIdx.x % CS_COLS, g = threadIdx.x / CS_COLS;
+  const int i = blk * CS_COLS + c;
+  float acc = 0.f;
+  if (i < m) {
+#pragma unroll 4
+    for (int p = g; p < nparts; p += CS_GROUPS)
+      acc += parts[(int64_t)p * m + i];
+  }
+  sh[g * CS_COLS + c] = acc;
+  __syncthreads();
+  if (g == 0 && i < m) {
+    float s = sh[c];
+#pragma unroll
+    for (int q = 1; q < CS_GROUPS; ++q) s += sh[q * CS_COLS + c];
+    out[i] = f2bf(s);
+  }
+}
+
+__global__ void colsum_reduce_kernel(const float* __restrict__ parts,
+                                     bf16_t* __restrict__ out, int nparts,
+                                     int m) {
+  __shared__ float sh[NTHREADS];
+  colsum_reduce(parts, out, nparts, m, blockIdx.x, sh);
+}
+
+// The first cs_blocks blocks (0 without cs_out) reduce the column-sum parts
+// in the same launch, ahead of the blocks that reduce the product partials
+// so they are not its tail.
 __global__ void splitk_reduce_kernel(const float* __restrict__ parts,
                                      bf16_t* __restrict__ out, int nparts,
-                                     int64_t mn) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x * 4;
-  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+                                     int64_t mn, int cs_blocks,
+                                     const float* __restrict__ cs_parts,
+                                     bf16_t* __restrict__ cs_out,
+                                     int cs_nparts, int cs_m) {
+  __shared__ float sh[NTHREADS];
+  if ((int)blockIdx.x < cs_blocks) {  // block-uniform
+    colsum_reduce(cs_parts, cs_out, cs_nparts, cs_m, blockIdx.x, sh);
+    return;
+  }
+  const int blk = blockIdx.x - cs_blocks;
+  const int64_t stride = (int64_t)(gridDim.x - cs_blocks) * blockDim.x * 4;
+  for (int64_t i = ((int64_t)blk * blockDim.x + threadIdx.x) * 4;
        i < mn; i += stride) {
     if (i + 4 <= mn) {
       f32x4 sv = *reinterpret_cast<const f32x4*>(parts + i);
@@ -343,11 +392,14 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ parts,
 }
 
 void splitk_reduce(const float* parts, bf16_t* out, int nparts, int64_t mn,
-                   hipStream_t stream) {
-  const int blocks = (int)std::min<int64_t>(
-      (mn / 4 + NTHREADS - 1) / NTHREADS, 2048);
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(std::max(blocks, 1)),
-                     dim3(NTHREADS), 0, stream, parts, out, nparts, mn);
+                   const float* cs_parts, bf16_t* cs_out, int cs_nparts,
+                   int cs_m, hipStream_t stream) {
+  const int blocks = std::max(1, (int)std::min<int64_t>(
+      (mn / 4 + NTHREADS - 1) / NTHREADS, 2048));
+  const int cs_blocks = cs_out ? (cs_m + CS_COLS - 1) / CS_COLS : 0;
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(cs_blocks + blocks),
+                     dim3(NTHREADS), 0, stream, parts, out, nparts, mn,
+                     cs_blocks, cs_parts, cs_out, cs_nparts, cs_m);
 }
 
 }  // namespace
@@ -356,10 +408,19 @@ void gemm_bf16(const void* A, const void* B, void* C, void* c_pre,
                const void* bias, int M, int N, int K, int lda, int ldb,
                int ldc, int64_t stride_a, int64_t stride_b, int64_t stride_c,
                int batch, bool a_kc, bool b_kc, int epi, float* splitk_ws,
-               hipStream_t stream) {
+               void* colsum_out, hipStream_t stream) {
   const GemmPlan p = gemm_plan(M, N, K, lda, ldb, a_kc, b_kc, epi, batch);
   if (p.kernel == 0)
     throw std::runtime_error(std::string("gemm_bf16: ") + p.why_not);
+  const bool colsum = colsum_out != nullptr;
+  if (colsum) {
+    if (const char* why = colsum_why_not(p, a_kc, b_kc, batch))
+      throw std::runtime_error(std::string("gemm_bf16: ") + why);
+    if (splitk_ws == nullptr)
+      throw std::runtime_error(
+          "gemm_bf16: colsum_out needs a workspace of " +
+          std::to_string(gemm_ws_floats(p, M, N, true)) + " floats");
+  }
 
   // split-K: chunk z writes fp32 partials [M, N] at splitk_ws + z*M*N,
   // reduced into C (contiguous) by a second launch
@@ -367,7 +428,8 @@ void gemm_bf16(const void* A, const void* B, void* C, void* c_pre,
   const int64_t mn = (int64_t)M * N;
   if (split && splitk_ws == nullptr)
     throw std::runtime_error("gemm_bf16: split-K plan needs a workspace of " +
-                             std::to_string(p.split_k * mn) + " floats");
+                             std::to_string(gemm_ws_floats(p, M, N, false)) +
+                             " floats");
   if (split && ldc != N)
     throw std::runtime_error("gemm_bf16: split-K plan needs ldc == N");
   void* out = C;
@@ -375,11 +437,15 @@ void gemm_bf16(const void* A, const void* B, void* C, void* c_pre,
     out = splitk_ws;
     stride_c = mn;
   }
+  // column-sum parts follow the product partials in the workspace
+  float* cs_parts =
+      colsum ? splitk_ws + gemm_ws_floats(p, M, N, false) : nullptr;
+  const int cs_nparts = p.split_k * (N / plan::T256);
 
   if (p.kernel == plan::T256) {
     gemm256_bf16(A, B, out, c_pre, bias, M, N, K, lda, ldb, ldc, stride_a,
                  stride_b, stride_c, batch, /*k_outer=*/!a_kc, epi, p.split_k,
-                 p.k_chunk, stream);
+                 p.k_chunk, cs_parts, stream);
   } else {
     const int nbx = (N + BN - 1) / BN, nby = (M + BM - 1) / BM;
     const dim3 grid(nbx * nby, 1, split ? p.split_k : batch), block(NTHREADS);
@@ -408,7 +474,15 @@ void gemm_bf16(const void* A, const void* B, void* C, void* c_pre,
   }
   if (split) {
     HIP_CHECK(hipGetLastError());
-    splitk_reduce(splitk_ws, static_cast<bf16_t*>(C), p.split_k, mn, stream);
+    splitk_reduce(splitk_ws, static_cast<bf16_t*>(C), p.split_k, mn,
+                  cs_parts, static_cast<bf16_t*>(colsum_out), cs_nparts, M,
+                  stream);
+  } else if (colsum) {
+    HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(colsum_reduce_kernel,
+                       dim3((M + CS_COLS - 1) / CS_COLS), dim3(NTHREADS), 0,
+                       stream, cs_parts, static_cast<bf16_t*>(colsum_out),
+                       cs_nparts, M);
   }
 }
 

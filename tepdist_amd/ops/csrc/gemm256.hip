@@ -134,14 +134,26 @@ DEV_INLINE bf16x8 frag_fk(const bf16_t* slot, int df, int lane) {
     }                                                       \
   } while (0)
 
-template <int EPI, bool F32OUT = false, bool KO = false>
+// CS (k-outer, plain epilogue only): the block also sums A over the rows k
+// of its K-tiles, colsum[m] = sum_k A[k][m] (wgrad's bias gradient), from
+// the A fragments phase 0 already holds: one MFMA per fragment against a
+// ones B fragment, every column of the result the same sum. The N/256
+// blocks that share an A panel take its K-tiles in turn (block j the tiles
+// t of its chunk with t % nbx == j) and within a block wave (wm, wn) takes
+// m-fragments 2wn, 2wn+1 of its half, so each element is summed once. Each
+// block stores its fp32 part, zeros included, at colsum + (z*nbx + j)*M:
+// nothing to zero-fill, no atomics; the reduce kernels of gemm.hip add the
+// parts in fixed order.
+template <int EPI, bool F32OUT = false, bool KO = false, bool CS = false>
 __launch_bounds__(NTH, 1) __global__
 void gemm256_kernel(const bf16_t* __restrict__ A,
                     const bf16_t* __restrict__ B, void* __restrict__ Cv,
                     bf16_t* __restrict__ Cpre,
                     const bf16_t* __restrict__ bias, int M, int N, int K,
                     int lda, int ldb, int ldc, int64_t strideA,
-                    int64_t strideB, int64_t strideC, int k_chunk) {
+                    int64_t strideB, int64_t strideC, int k_chunk,
+                    float* __restrict__ colsum) {
+  static_assert(!CS || (KO && EPI == EPI_NONE), "CS: k-outer, plain epilogue");
   bf16_t* C = static_cast<bf16_t*>(Cv);
   float* Cf = static_cast<float*>(Cv);
   int kbeg = 0, kend = K;
@@ -206,6 +218,17 @@ void gemm256_kernel(const bf16_t* __restrict__ A,
   }
   RAW_BAR();
 
+  // CS: this block's turn comes every nbx-th K-tile, starting at its n-tile
+  // index; wave-uniform scalars, so the extra MFMAs sit behind scalar tests
+  const int cs_wn = CS ? __builtin_amdgcn_readfirstlane(wn) : 0;
+  int cs_next = swz % nbx;
+  f32x4 cs[2] = {};
+  bf16x8 ones;
+  if (CS) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) ones[e] = f2bf(1.0f);
+  }
+
   bf16x8 af[8][2];
   for (int t = 0; t < nk; ++t) {
     if (t + 1 == nk && nk > 1) {
@@ -242,6 +265,19 @@ void gemm256_kernel(const bf16_t* __restrict__ A,
         for (int kk = 0; kk < 2; ++kk)
           acc[mi][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
               af[mi][kk], bf0[kk], acc[mi][0], 0, 0, 0);
+      if (CS && t == cs_next) {
+        cs_next += nbx;
+#pragma unroll
+        for (int w = 0; w < 4; ++w)  // af is indexed statically: 4 cases
+          if (w == cs_wn) {
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+              for (int h = 0; h < 2; ++h)
+                cs[h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                    af[2 * w + h][kk], ones, cs[h], 0, 0, 0);
+          }
+      }
       __builtin_amdgcn_s_setprio(0);
       RAW_BAR();
     }
@@ -269,6 +305,18 @@ void gemm256_kernel(const bf16_t* __restrict__ A,
       __builtin_amdgcn_s_setprio(0);
       if (p == 3) VMCNT6();  // tile boundary: t+1 fully resident
       RAW_BAR();
+    }
+  }
+
+  // ---- column sums: all 16 result columns are equal, the lanes of column
+  // 0 store rows 4*(lane>>4) + e of m-fragments 2wn, 2wn+1
+  if (CS) {
+    float* part = colsum +
+        ((int64_t)(F32OUT ? blockIdx.z : 0) * nbx + swz % nbx) * M + m0 +
+        wm * 128 + wn * 32 + 4 * (lane >> 4);
+    if ((lane & 15) == 0) {
+      *reinterpret_cast<f32x4*>(part) = cs[0];
+      *reinterpret_cast<f32x4*>(part + 16) = cs[1];
     }
   }
 
@@ -367,35 +415,47 @@ void gemm256_kernel(const bf16_t* __restrict__ A,
 
 // Launches what gemm_plan() planned for the 256 kernel: split_k > 1 writes
 // fp32 partials (C is then the workspace), chunk z at C + z*stride_c.
-// k_outer: both operands stored [K][F] (plain epilogue only).
+// k_outer: both operands stored [K][F] (plain epilogue only). colsum_parts
+// (k_outer and batch 1 only, else null): split_k * (N/256) vectors of M
+// floats, all written, whose sum over the parts is A's column sums.
 void gemm256_bf16(const void* A, const void* B, void* C, void* c_pre,
                   const void* bias, int M, int N, int K, int lda, int ldb,
                   int ldc, int64_t stride_a, int64_t stride_b,
                   int64_t stride_c, int batch, bool k_outer, int epi,
-                  int split_k, int k_chunk, hipStream_t stream) {
+                  int split_k, int k_chunk, float* colsum_parts,
+                  hipStream_t stream) {
   const bool split = split_k > 1;
   const dim3 grid((N / BN) * (M / BM), 1, split ? split_k : batch), block(NTH);
   const bf16_t* a = static_cast<const bf16_t*>(A);
   const bf16_t* b = static_cast<const bf16_t*>(B);
   bf16_t* cp = static_cast<bf16_t*>(c_pre);
   const bf16_t* bi = static_cast<const bf16_t*>(bias);
-#define G256(E, F32, KO)                                                    \
-  hipLaunchKernelGGL((gemm256_kernel<E, F32, KO>), grid, block, 0, stream, \
-                     a, b, C, cp, bi, M, N, K, lda, ldb, ldc, stride_a,    \
-                     stride_b, stride_c, k_chunk)
+#define G256(E, F32, KO, CS)                                               \
+  hipLaunchKernelGGL((gemm256_kernel<E, F32, KO, CS>), grid, block, 0,     \
+                     stream, a, b, C, cp, bi, M, N, K, lda, ldb, ldc,      \
+                     stride_a, stride_b, stride_c, k_chunk, colsum_parts)
   if (k_outer) {
     if (epi != EPI_NONE)
       throw std::runtime_error(
           "gemm256_bf16: k-outer operands have only the plain epilogue");
-    if (split) { G256(EPI_NONE, true, true); }
-    else { G256(EPI_NONE, false, true); }
-  } else if (split) { G256(EPI_NONE, true, false); }
+    if (colsum_parts && batch != 1)
+      throw std::runtime_error("gemm256_bf16: column sums need batch 1");
+    if (colsum_parts) {
+      if (split) { G256(EPI_NONE, true, true, true); }
+      else { G256(EPI_NONE, false, true, true); }
+    }
+    else if (split) { G256(EPI_NONE, true, true, false); }
+    else { G256(EPI_NONE, false, true, false); }
+  } else if (colsum_parts) {
+    throw std::runtime_error(
+        "gemm256_bf16: column sums need two k-outer operands");
+  } else if (split) { G256(EPI_NONE, true, false, false); }
   else switch (epi) {
-    case EPI_NONE: G256(EPI_NONE, false, false); break;
-    case EPI_BIAS: G256(EPI_BIAS, false, false); break;
-    case EPI_BIAS_GELU: G256(EPI_BIAS_GELU, false, false); break;
-    case EPI_GELU: G256(EPI_GELU, false, false); break;
-    case EPI_DGELU: G256(EPI_DGELU, false, false); break;
+    case EPI_NONE: G256(EPI_NONE, false, false, false); break;
+    case EPI_BIAS: G256(EPI_BIAS, false, false, false); break;
+    case EPI_BIAS_GELU: G256(EPI_BIAS_GELU, false, false, false); break;
+    case EPI_GELU: G256(EPI_GELU, false, false, false); break;
+    case EPI_DGELU: G256(EPI_DGELU, false, false, false); break;
   }
 #undef G256
 }

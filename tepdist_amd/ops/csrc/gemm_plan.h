@@ -121,4 +121,25 @@ inline GemmPlan gemm_plan(int M, int N, int K, int lda, int ldb, bool a_kc,
   return {T128, split_k, k_chunk, nullptr};
 }
 
+// Column sums of A (colsum[m] = sum over k of A[k][m], wgrad's bias
+// gradient) come only from the 256 kernel on two k-outer operands: nullptr
+// when plan `p` of a call with these layouts can produce them, else why not.
+inline const char* colsum_why_not(const GemmPlan& p, bool a_kc, bool b_kc,
+                                  int batch) {
+  if (p.kernel != plan::T256 || a_kc || b_kc || batch != 1)
+    return "colsum_out needs the 256 kernel on two k-outer operands (A "
+           "stored [K][M], B stored [K][N], M and N multiples of 256, K a "
+           "multiple of 64 and >= 128, 16-byte-aligned rows, epi 0, batch 1)";
+  return nullptr;
+}
+
+// Floats of fp32 workspace that plan `p` of an [M, N] call needs, the only
+// place that knows: split_k * M * N product partials when K is split, then,
+// with column sums, one vector of M floats per part (split chunk, n-tile).
+inline int64_t gemm_ws_floats(const GemmPlan& p, int M, int N, bool colsum) {
+  int64_t n = p.split_k > 1 ? int64_t(p.split_k) * M * N : 0;
+  if (colsum) n += int64_t(p.split_k) * (N / plan::T256) * M;
+  return n;
+}
+
 }  // namespace tepdist

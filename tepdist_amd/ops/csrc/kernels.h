@@ -26,19 +26,29 @@ using bf16 = __hip_bfloat16;
 // split_k * M * N floats and ldc must be N: the chunks write fp32 partials
 // there and a second launch reduces them into C. splitk_ws may be null
 // otherwise.
+// colsum_out (bf16 [M], may be null): also returns A's column sums,
+// colsum[m] = sum over k of A[k][m] (wgrad's bias gradient), formed by the
+// 256 kernel from the fragments it holds anyway. Only for a 256-kernel plan
+// on two k-outer operands (colsum_why_not, gemm_plan.h), else it throws.
+// The workspace then holds gemm_ws_floats(plan, M, N, true) floats, split
+// or not; no part of it needs zeroing and no atomics run, so the sums are
+// the same bits on every call.
 void gemm_bf16(const void* A, const void* B, void* C, void* c_pre,
                const void* bias, int M, int N, int K, int lda, int ldb,
                int ldc, int64_t stride_a, int64_t stride_b, int64_t stride_c,
                int batch, bool a_kc, bool b_kc, int epi, float* splitk_ws,
-               hipStream_t stream);
+               void* colsum_out, hipStream_t stream);
 // Launcher of the deep-pipelined 256x256 kernel, for gemm_bf16 only: runs
 // the plan it is given (split_k > 1: C is the fp32 workspace). k_outer:
 // both operands stored [K][F] (a_kc = b_kc = false), epi 0 only.
+// colsum_parts (k_outer, batch 1; else null): fp32 column-sum parts of A,
+// split_k * (N/256) vectors of M floats, for gemm_bf16's reduce.
 void gemm256_bf16(const void* A, const void* B, void* C, void* c_pre,
                   const void* bias, int M, int N, int K, int lda, int ldb,
                   int ldc, int64_t stride_a, int64_t stride_b,
                   int64_t stride_c, int batch, bool k_outer, int epi,
-                  int split_k, int k_chunk, hipStream_t stream);
+                  int split_k, int k_chunk, float* colsum_parts,
+                  hipStream_t stream);
 
 // --- Transpose -------------------------------------------------------------
 // out[c][r] = in[r][c] per batch (strides in elements).

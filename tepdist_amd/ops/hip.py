@@ -98,7 +98,10 @@ def _pick_backend(key, hip_fn, blt_fn):
 def _gemm_raw(a: torch.Tensor, b_stored: torch.Tensor, a_kc: bool, b_kc: bool,
               M: int, N: int, K: int, lda: int, ldb: int,
               sa: int, sb: int, batch: int, bias=None, epi: int = 0,
-              out=None, out_pre=None, device=None):
+              out=None, out_pre=None, device=None, colsum_out=None):
+    """colsum_out (bf16 [M]): also receives the column sums of a k-outer A
+    (A stored [K][M]), where the plan gives the 256 kernel; ext.gemm throws
+    elsewhere."""
     dev = device if device is not None else a.device
     c = out if out is not None else torch.empty(
         (batch, M, N) if batch > 1 else (M, N), dtype=BF16, device=dev)
@@ -106,14 +109,16 @@ def _gemm_raw(a: torch.Tensor, b_stored: torch.Tensor, a_kc: bool, b_kc: bool,
     if epi >= 2 and cp is None:
         cp = torch.empty_like(c)
 
-    # kernel choice and split-K are planned in csrc/gemm_plan.h; a split
-    # plan needs fp32 room for its partials (ext.gemm reduces them into c)
-    split_k = ext.gemm_plan(M, N, K, lda, ldb, a_kc, b_kc, epi, batch)[1]
-    ws = torch.empty(split_k * M * N, dtype=torch.float32, device=dev) \
-        if split_k > 1 else None
+    # kernel choice and split-K are planned in csrc/gemm_plan.h, which also
+    # sizes the fp32 room for a split plan's partials and for column-sum
+    # parts (ext.gemm reduces both; none of it needs zeroing)
+    ws_floats = ext.gemm_ws_floats(M, N, K, lda, ldb, a_kc, b_kc, epi, batch,
+                                   colsum_out is not None)
+    ws = torch.empty(ws_floats, dtype=torch.float32, device=dev) \
+        if ws_floats else None
     ext.gemm(a.data_ptr(), b_stored.data_ptr(), c.data_ptr(), _p(cp), _p(bias),
              M, N, K, lda, ldb, N, sa, sb, M * N, batch, a_kc, b_kc, epi,
-             _p(ws), _stream())
+             _p(ws), _stream(), _p(colsum_out))
     return c, cp
 
 
@@ -264,8 +269,7 @@ def mlp_bwd(dy, x, w1, w2, h, pre):
         # proj dgrad with the DGELU_BGRAD epilogue: one library call
         # yields dgelu'd dh AND the fc bias grad
         dh, db1 = _blt_mlp_dgelu(dy, w2, pre)
-        dw2 = matmul(dy.t(), h)      # measured: in-place hand wgrad or library
-        db2 = _bias_sum(dy)
+        dw2, db2 = wgrad(dy, h, True)
         dx, dw1, _ = linear_bwd(dh, x, w1, False, "none", None)
         out["r"] = (dx, dw1, db1, dw2, db2)
 
@@ -287,8 +291,7 @@ def mlp_bwd(dy, x, w1, w2, h, pre):
         dh, _ = _gemm_raw(dy, w2T, True, True, M, K2, N2, N2, N2, 0, 0, 1,
                           epi=4, out_pre=pre)
         db1 = _bias_sum(dh)
-        dw2 = matmul(dy.t(), h)      # measured: in-place hand wgrad or library
-        db2 = _bias_sum(dy)
+        dw2, db2 = wgrad(dy, h, True)
         dx, dw1, _ = linear_bwd(dh, x, w1, False, "none", None)
         out["r"] = (dx, dw1, db1, dw2, db2)
 
@@ -330,6 +333,41 @@ def transpose2d(t: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _wgrad_in_place(dyl: torch.Tensor, x: torch.Tensor) -> bool:
+    """Whether the plan gives wgrad of dyl [M,N] and x [M,K], two k-outer
+    operands, the 256 kernel that reads them as they lie."""
+    (M, N), K = dyl.shape, x.shape[1]
+    return dyl.stride(-1) == 1 and x.stride(-1) == 1 and ext.gemm_plan(
+        N, K, M, dyl.stride(0), x.stride(0), False, False, 0, 1)[0] == 256
+
+
+def wgrad(dyl: torch.Tensor, x: torch.Tensor, has_bias: bool):
+    """(dw, db) = (dyl^T @ x, column sums of dyl or None). Where the 256
+    kernel reads both operands in place its column-sum variant forms db from
+    the dy fragments it holds anyway: one hand call, no second pass over
+    dyl, no atomics. Measured per shape against the library GEMM plus the
+    streaming bias sum, bias and bias-less sites apart."""
+    M, N = dyl.shape
+    K = x.shape[1]
+    def _db():  # the streaming pass wants whole rows
+        return _bias_sum(dyl.contiguous()) if has_bias else None
+
+    if not _wgrad_in_place(dyl, x):
+        return matmul(dyl.t(), x), _db()
+
+    def _hand():
+        db = torch.empty(N, dtype=BF16, device=dyl.device) \
+            if has_bias else None
+        dw = _gemm_raw(dyl, x, False, False, N, K, M, dyl.stride(0),
+                       x.stride(0), 0, 0, 1, colsum_out=db)[0]
+        return dw, db
+
+    def _lib():
+        return torch.matmul(dyl.t(), x), _db()
+
+    return _pick_backend(("lin_bw", M, N, K, has_bias), _hand, _lib)()
+
+
 def linear_bwd(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor,
                has_bias: bool, act: str, pre_act: Optional[torch.Tensor]):
     dy = dy.contiguous()
@@ -341,8 +379,7 @@ def linear_bwd(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor,
     # plan gives such a call the 256 kernel, it reads dy and x in place: no
     # activation transpose, and dgrad and wgrad each take the backend that
     # measured faster for them (inside a graph capture both stay hand).
-    if x.stride(-1) == 1 and \
-            ext.gemm_plan(N, K, M, N, x.stride(0), False, False, 0, 1)[0] == 256:
+    if _wgrad_in_place(dy, x):
         if act == "gelu":
             dyl = torch.empty_like(dy)
             ext.gelu_bwd(dy.data_ptr(), pre_act.data_ptr(), dyl.data_ptr(),
@@ -354,15 +391,10 @@ def linear_bwd(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor,
             wT = transpose2d(w)    # [K, N]: the weight, a few microseconds
             return _gemm_raw(dyl, wT, True, True, M, K, N, N, N, 0, 0, 1)[0]
 
-        def _dw_hip():
-            return _gemm_raw(dyl, x, False, False, N, K, M, N, x.stride(0),
-                             0, 0, 1)[0]
-
         dx = _pick_backend(("lin_bx", M, N, K), _dx_hip,
                            lambda: torch.matmul(dyl, w))()
-        dw = _pick_backend(("lin_bw", M, N, K), _dw_hip,
-                           lambda: torch.matmul(dyl.t(), x))()
-        return dx, dw, _bias_sum(dyl) if has_bias else None
+        dw, db = wgrad(dyl, x, has_bias)
+        return dx, dw, db
 
     def _hip():
         # canonicalize to KC x KC: one tuned GEMM schedule serves every
