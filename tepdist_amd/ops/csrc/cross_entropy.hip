@@ -61,9 +61,10 @@ void ce_fwd_kernel(const bf16_t* __restrict__ logits,
       const float lse = m2 + __logf(s);
       lse_out[row] = lse;
       const int64_t t = targets[row];
-      // t < 0: either the ignore index or a "no target in this vocab
-      // shard" sentinel (vocab-parallel CE) -> no target-logit read
-      nll[row] = (t < 0) ? 0.f : lse - bf2f(lr[t]);
+      // t == ignore_index (any sign, e.g. a pad id) or t < 0, the "no
+      // target in this vocab shard" sentinel of vocab-parallel CE -> no
+      // loss and no target-logit read
+      nll[row] = (t < 0 || t == ignore_index) ? 0.f : lse - bf2f(lr[t]);
     }
     __syncthreads();
   }

@@ -605,6 +605,11 @@ def softmax_fwd(scores: torch.Tensor, scale: float = 1.0,
                 causal: bool = False) -> torch.Tensor:
     scores = scores.contiguous()
     sq, sk = scores.shape[-2], scores.shape[-1]
+    if causal and sq > sk:
+        # query q sees keys <= q + (sk - sq): the first sq - sk queries
+        # would see no key at all (an empty softmax, NaN in the kernel)
+        raise ValueError(f"causal softmax needs sq <= sk, got sq={sq} "
+                         f"sk={sk}")
     rows = scores.numel() // sk
     p = torch.empty_like(scores)
     ext.softmax_fwd(scores.data_ptr(), p.data_ptr(), rows, sk, sq, scale,
@@ -987,9 +992,14 @@ class AdamWMT:
                      1.0, self.hyper.data_ptr(), _stream())
 
     def set_hyper(self, lr, beta1, beta2, step_no):
-        vals = torch.tensor([lr, 1.0 / (1.0 - beta1 ** step_no),
-                             1.0 / (1.0 - beta2 ** step_no), 0.0],
+        # the eager launcher rounds bc1/bc2 to fp32 and then forms
+        # 1.0f / bc; do the same here (not fp32(1 / bc) from a double
+        # quotient, which differs in the last bit, e.g. at bc2 = 0.001) so
+        # a replayed step equals the eager one bit for bit
+        vals = torch.tensor([lr, 1.0 - beta1 ** step_no,
+                             1.0 - beta2 ** step_no, 0.0],
                             dtype=torch.float32)
+        vals[1:3] = torch.ones(2, dtype=torch.float32) / vals[1:3]
         self.hyper.copy_(vals, non_blocking=True)
 
 

@@ -97,8 +97,10 @@ def layernorm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
 
 
 def layernorm_bwd(dy: torch.Tensor, x: torch.Tensor, gamma: torch.Tensor,
-                  mean: torch.Tensor, rstd: torch.Tensor):
-    """Returns (dx, dgamma, dbeta)."""
+                  mean: torch.Tensor, rstd: torch.Tensor,
+                  dsum: Optional[torch.Tensor] = None):
+    """Returns (dx, dgamma, dbeta). With dsum, dx = dsum + d(ln)/dx summed
+    in fp32 and rounded once (the add + LayerNorm backward)."""
     x32 = x.float()
     dy32 = dy.float()
     xhat = (x32 - mean.unsqueeze(-1)) * rstd.unsqueeze(-1)
@@ -109,7 +111,23 @@ def layernorm_bwd(dy: torch.Tensor, x: torch.Tensor, gamma: torch.Tensor,
     c1 = g.mean(dim=-1, keepdim=True)
     c2 = (g * xhat).mean(dim=-1, keepdim=True)
     dx = (g - c1 - xhat * c2) * rstd.unsqueeze(-1)
+    if dsum is not None:
+        dx = dx + dsum.float()
     return dx.to(x.dtype), dgamma.to(gamma.dtype), dbeta.to(gamma.dtype)
+
+
+def add_layernorm_fwd(x: torch.Tensor, res: torch.Tensor,
+                      gamma: torch.Tensor, beta: torch.Tensor,
+                      eps: float = 1e-5):
+    """s = x + res (fp32 sum rounded once), y = ln(s) with statistics over
+    the rounded s. Returns (s, y, mean, rstd)."""
+    s = (x.float() + res.float()).to(x.dtype)
+    return (s,) + layernorm_fwd(s, gamma, beta, eps)
+
+
+def add_layernorm_bwd(dy, dsum, s, gamma, mean, rstd):
+    """Returns (dx, dgamma, dbeta); dsum may be None."""
+    return layernorm_bwd(dy, s, gamma, mean, rstd, dsum=dsum)
 
 
 # --------------------------------------------------------------------------
@@ -123,6 +141,10 @@ def softmax_fwd(scores: torch.Tensor, scale: float = 1.0,
     s32 = scores.float() * scale
     if causal:
         sq, sk = scores.shape[-2], scores.shape[-1]
+        if sq > sk:
+            # the first sq - sk queries would see no key at all (NaN rows)
+            raise ValueError(f"causal softmax needs sq <= sk, got sq={sq} "
+                             f"sk={sk}")
         mask = torch.ones(sq, sk, dtype=torch.bool, device=scores.device).tril(sk - sq)
         s32 = s32.masked_fill(~mask, float("-inf"))
     p = torch.softmax(s32, dim=-1)
