@@ -1,5 +1,5 @@
-"""Float64 oracles for the row and elementwise ops, and the bound the HIP
-kernels (and the fp32 ops/reference.py) are held to.
+"""Float64 oracles for the row and elementwise ops and for attention, and
+the bound the HIP kernels (and the fp32 ops/reference.py) are held to.
 
 Every function takes the tensors the kernel takes (bf16 / fp32 / int, on
 any device), moves them to the CPU, upcasts to float64 and evaluates the
@@ -176,6 +176,64 @@ def softmax_bwd(dp, p, scale: float = 1.0):
     """ds = scale * p * (dp - sum_k dp_k p_k), from the saved bf16 p."""
     dp, p = f64(dp), f64(p)
     return f32r(scale) * p * (dp - (dp * p).sum(-1, keepdim=True))
+
+
+# --------------------------------------------------------------------------
+# Attention (the flash kernels of csrc/attention.hip)
+# --------------------------------------------------------------------------
+
+NO_LSE = -3.0e38      # what the kernels store for a row that saw no key
+
+
+def attention_scores(q, k, causal: bool, scale: float):
+    """Returns (s, allowed): s = scale * q k^T in float64, [B, H, S, S],
+    and the boolean [S, S] mask of the keys a query may see (causal: key
+    j <= query i). s is left unmasked."""
+    S = q.shape[-2]
+    s = f64(q) @ f64(k).transpose(-1, -2) * f32r(scale)
+    i = torch.arange(S)
+    allowed = (i[None, :] <= i[:, None]) if causal else \
+        torch.ones(S, S, dtype=torch.bool)
+    return s, allowed
+
+
+def attention_fwd(q, k, v, causal: bool, scale: float):
+    """Returns (out, lse, p): p = softmax over the allowed keys of
+    scale * q k^T [B, H, S, S], out = p v, lse [B, H, S] the logsumexp of
+    the allowed scaled scores."""
+    s, allowed = attention_scores(q, k, causal, scale)
+    s = s.masked_fill(~allowed, -math.inf)
+    m = s.max(-1, keepdim=True).values
+    e = (s - m).exp()
+    l = e.sum(-1, keepdim=True)
+    p = e / l
+    return p @ f64(v), (m + l.log())[..., 0], p
+
+
+def attention_p_given_lse(q, k, lse, causal: bool, scale: float):
+    """p^ = exp(scale * q k^T - lse) where the key is allowed, 0 where it
+    is masked or the row's lse is the NO_LSE sentinel: the probabilities
+    the backward forms from the lse it was GIVEN (any shape that reshapes
+    to [B, H, S]). With a global lse of more keys a row sums to under 1."""
+    s, allowed = attention_scores(q, k, causal, scale)
+    l = f64(lse).reshape(s.shape[:-1])[..., None]
+    valid = allowed & (l > -1.0e38)
+    return torch.where(valid, s - torch.where(valid, l, torch.zeros_like(l)),
+                       torch.full_like(s, -math.inf)).exp()
+
+
+def attention_bwd(dout, q, k, v, out, lse, causal: bool, scale: float):
+    """Returns (dq, dk, dv) as a function of the (out, lse) the backward
+    was given (as softmax_bwd is of its p): dS = p^ * (dout v^T - delta),
+    delta = sum_d dout * out, dq = scale * dS k, dk = scale * dS^T q,
+    dv = p^^T dout."""
+    ph = attention_p_given_lse(q, k, lse, causal, scale)
+    do = f64(dout)
+    delta = (do * f64(out)).sum(-1, keepdim=True)
+    ds = ph * (do @ f64(v).transpose(-1, -2) - delta)
+    sc = f32r(scale)
+    return sc * ds @ f64(k), sc * ds.transpose(-1, -2) @ f64(q), \
+        ph.transpose(-1, -2) @ do
 
 
 # --------------------------------------------------------------------------

@@ -631,6 +631,32 @@ def softmax_bwd(dp: torch.Tensor, p: torch.Tensor,
 _ATTN_IMPL = os.environ.get("TEPDIST_ATTN", "flash")
 
 
+def _check_attention_operands(name: str, q: torch.Tensor, **others):
+    """The flash launch takes B, H, S, D from q alone and reads every
+    operand as bf16 of that shape: anything else would be misread (a
+    shorter k out of bounds), so it is refused before any launch."""
+    if q.dim() != 4:
+        raise ValueError(f"{name}: q must be [B, H, S, D], got "
+                         f"{tuple(q.shape)}")
+    for what, t in (("q", q),) + tuple(others.items()):
+        if t.dtype != torch.bfloat16:
+            raise ValueError(f"{name}: {what} is {t.dtype}, the flash "
+                             "kernels are bf16-only")
+        if t.shape != q.shape:
+            raise ValueError(f"{name}: {what} is {tuple(t.shape)}, q is "
+                             f"{tuple(q.shape)}")
+        if t.device != q.device:
+            raise ValueError(f"{name}: {what} is on {t.device}, q on "
+                             f"{q.device}")
+
+
+def _check_lse(name: str, lse: torch.Tensor, bh: int, S: int):
+    if lse.dtype != torch.float32 or lse.numel() != bh * S:
+        raise ValueError(f"{name}: lse must be fp32 with {bh} x {S} "
+                         f"elements, got {lse.dtype} {tuple(lse.shape)}")
+    return lse.contiguous()
+
+
 def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                   causal: bool = True):
     """Fused flash attention (no S x S matrix in HBM); saves (out, lse)
@@ -643,6 +669,7 @@ def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
         p = softmax_fwd(scores, scale=scale, causal=causal)
         out = matmul(p, v)
         return out, (p,)
+    _check_attention_operands("attention_fwd", q, k=k, v=v)
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
     out = torch.empty_like(q)
     lse = torch.empty(B * H, S, dtype=torch.float32, device=q.device)
@@ -666,11 +693,17 @@ def attention_bwd(dout: torch.Tensor, q, k, v, residuals,
         dk = matmul(ds.transpose(-1, -2), q)
         return dq, dk, dv
     out, lse = residuals
-    dout = dout.contiguous()
+    _check_attention_operands("attention_bwd", q, k=k, v=v, out=out,
+                              dout=dout)
+    lse = _check_lse("attention_bwd", lse, B * H, S)
+    # the launch below passes contiguous strides: whatever views the caller
+    # saved (a transposed q from reshape(B, S, H, D).transpose(1, 2)) are
+    # made contiguous first, a no-op for tensors that already are, and the
+    # gradients are allocated contiguous, not with a view's strides
+    q, k, v, out, dout = (t.contiguous() for t in (q, k, v, out, dout))
     delta = torch.empty(B * H, S, dtype=torch.float32, device=q.device)
-    dq = torch.empty_like(q)
-    dk = torch.empty_like(k)
-    dv = torch.empty_like(v)
+    dq, dk, dv = (torch.empty(q.shape, dtype=q.dtype, device=q.device)
+                  for _ in range(3))
     sd = (H * S * D, S * D, D)
     ext.attention_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(),
                       out.data_ptr(), dout.data_ptr(), lse.data_ptr(),
@@ -781,15 +814,28 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
     return out
 
 
+def _packed_dims(name: str, qkv: torch.Tensor, heads: int):
+    """(B, S, D) of a packed qkv [B, S, 3*heads*D]; anything that does not
+    split that way is refused (the launch would take D = d // heads and
+    read past the heads)."""
+    if qkv.dim() != 3 or heads < 1 or qkv.shape[-1] % (3 * heads):
+        raise ValueError(f"{name}: qkv must be [B, S, 3 * heads * D], got "
+                         f"{tuple(qkv.shape)} for {heads} heads")
+    return qkv.shape[0], qkv.shape[1], qkv.shape[-1] // (3 * heads)
+
+
 def attention_qkv_fwd(qkv: torch.Tensor, heads: int, causal: bool = True):
     """Packed-projection attention: qkv [B, S, 3*H*D] (q|k|v each [H][D]),
     out [B, S, H*D] — the flash kernels read/write the packed layout
     directly (no transpose copies)."""
-    B, S, d3 = qkv.shape
-    d = d3 // 3
-    D = d // heads
+    B, S, D = _packed_dims("attention_qkv_fwd", qkv, heads)
+    d = heads * D
+    d3 = 3 * d
     if D not in (64, 128) or _ATTN_IMPL == "composed":
         return None  # caller falls back to the split path
+    if qkv.dtype != torch.bfloat16:
+        raise ValueError(f"attention_qkv_fwd: qkv is {qkv.dtype}, the "
+                         "flash kernels are bf16-only")
     qkv = qkv.contiguous()
     scale = 1.0 / math.sqrt(D)
     out = torch.empty(B, S, d, dtype=qkv.dtype, device=qkv.device)
@@ -817,10 +863,24 @@ def attention_qkv_bwd(dout: torch.Tensor, qkv: torch.Tensor, heads: int,
             return t.transpose(1, 2).reshape(B, S, d)
         return torch.cat([back(dq), back(dk), back(dv)], dim=-1)
     out, lse = residuals
+    _packed_dims("attention_qkv_bwd", qkv, heads)
+    if D not in (64, 128):
+        raise ValueError(f"attention_qkv_bwd: flash residuals with head dim "
+                         f"{D}; the flash kernels take 64 or 128")
+    for what, t in (("qkv", qkv), ("out", out), ("dout", dout)):
+        if t.dtype != torch.bfloat16 or t.device != qkv.device:
+            raise ValueError(f"attention_qkv_bwd: {what} is {t.dtype} on "
+                             f"{t.device}; the flash kernels take bf16 on "
+                             "one device")
+    for what, t in (("out", out), ("dout", dout)):
+        if t.shape != (B, S, d):
+            raise ValueError(f"attention_qkv_bwd: {what} is "
+                             f"{tuple(t.shape)}, expected {(B, S, d)}")
+    lse = _check_lse("attention_qkv_bwd", lse, B * heads, S)
     scale = 1.0 / math.sqrt(D)
-    dout = dout.contiguous()
+    qkv, out, dout = qkv.contiguous(), out.contiguous(), dout.contiguous()
     delta = torch.empty(B * heads, S, dtype=torch.float32, device=qkv.device)
-    dqkv = torch.empty_like(qkv)
+    dqkv = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)
     qs = (S * d3, D, d3)
     os_ = (S * d, D, d)
     base = qkv.data_ptr()
