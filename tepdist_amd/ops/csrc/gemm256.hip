@@ -15,8 +15,56 @@
 // A), B(t,q_p) at t.ph_p; stages run A(t+2,q01)@t.ph1, A(t+2,q23)@t.ph2,
 // B(t+2,q01)@t.ph3, B(t+2,q23)@(t+1).ph0. All barriers are RAW s_barrier
 // (no vmcnt drain: __syncthreads would wait the in-flight DMAs to 0) and a
-// single counted s_waitcnt vmcnt(6) + barrier per K-tile boundary keeps 6
-// quarter-units (3 "half-tiles") in flight.
+// single counted s_waitcnt vmcnt(6) per K-tile keeps 6 quarter-units (3
+// "half-tiles") in flight.
+//
+// Stagger. Waves w and w+4 share a SIMD and differ in wm, so in lockstep
+// both read LDS together and issue MFMAs together. Waves 4..7 (the "late"
+// half, wm == 1) therefore take one extra barrier in front of the K loop
+// and waves 0..3 (the "early" half) one behind it: on every SIMD one wave is
+// in its MFMA cluster while its partner reads fragments and stages. Number
+// the phases j = 4t + p, call phase j's read+stage segment R_j and its MFMA
+// segment M_j, and count barrier instances so that the early half runs R_j
+// between instances 2j-1 and 2j and M_j between 2j and 2j+1; the late half
+// runs both one instance later. Every wave stages a share of every unit, and
+// a wave's counted wait covers its own DMAs only. Two rules follow:
+//  RAW  a wait in R_w is passed by the late half before instance 2w+1, which
+//       the early half passes before R_{w+1}: waits sit in R segments (in
+//       front of the phase's first barrier) and the first read of what they
+//       retire is one phase later. A wait in M_w would be too late.
+//  WAR  reads issued in R_r retire at the lgkmcnt(0) that heads M_r. For
+//       early readers that is before instance 2r+1, and the earliest
+//       restage, the early half's R_{r+1}, comes after it. For late readers
+//       it is before 2r+2 only, so their slot may be restaged in R_{r+2}, or
+//       in R_{r+1} if the lgkmcnt(0) stands in front of R_r's barrier.
+// Every staged unit of tile t, j0 = 4t (steady state):
+//   unit      staged    retired by     read     readers  restaged
+//   A(t,q01)  R_{j0-7}  wait R_{j0-1}  R_{j0}   early    R_{j0+1}  r+1, early
+//   A(t,q23)  R_{j0-6}  wait R_{j0-1}  R_{j0}   late     R_{j0+2}  r+2
+//   B(t,q0)   R_{j0-5}  wait R_{j0-1}  R_{j0}   both     R_{j0+3}  r+3
+//   B(t,q1)   R_{j0-5}  wait R_{j0-1}  R_{j0+1} both     R_{j0+3}  r+2
+//   B(t,q2)   R_{j0-4}  wait R_{j0-1}  R_{j0+2} both     R_{j0+4}  r+2
+//   B(t,q3)   R_{j0-4}  wait R_{j0-1}  R_{j0+3} both     R_{j0+4}  r+1 (*)
+// (*) phase 3 waits lgkmcnt(0) in front of its first barrier, both layouts.
+// Each unit is read in one phase only. The wait of R_{j0-1}, phase 3 of tile
+// t-1, is vmcnt(6) behind stage_b(t+1, 0): A(t+1) and B(t+1,q01) stay in
+// flight, all of tile t is retired.
+//  Prologue: tile 0 and A(1), B(1,q01) are staged, vmcnt(6) retires tile 0
+//   in front of the barrier every wave takes before R_0; no slot is reused.
+//   A(1), B(1,q01) and B(1,q23) (staged in R_0) retire at the wait of R_3.
+//  nk == 2: nothing is staged after R_0 and R_3 waits vmcnt(0).
+//  nk == 3: R_1..R_3 stage A(2), B(2,q01), vmcnt(6) retires tile 1; R_4
+//   restages B(0,q23) as B(2,q23) by (*); R_7 waits vmcnt(0).
+//  Last tile: tile nk-2 stages nothing in phases 1..3, so no count would
+//   push B(nk-1,q23) out; its phase 3 waits vmcnt(0), one phase before the
+//   first read of tile nk-1. (A vmcnt(0) + barrier in front of the last
+//   tile would let the early half read past a wait the late half has not
+//   reached.)
+//  Epilogue: after the early half's extra barrier every wave waits
+//   lgkmcnt(0) and takes one more; no DMA is in flight and every fragment
+//   read has retired when the output image overwrites the slots.
+// Each wave issues 16 MFMAs per phase; the 4 column-sum MFMAs fall to every
+// wave of a block in the same phase 0, so the halves stay equal.
 //
 // Two operand layouts, both with M,N % 256 == 0, K % 64 == 0, 16B-aligned
 // rows and >= 2 K-tiles per chunk (gemm_plan.h decides when that holds,
@@ -217,6 +265,10 @@ void gemm256_kernel(const bf16_t* __restrict__ A,
     VMCNT6();
   }
   RAW_BAR();
+  // the stagger (header): waves 4..7 start one barrier late, waves 0..3
+  // make it up after the loop
+  const bool late = __builtin_amdgcn_readfirstlane(threadIdx.x) >= 256;
+  if (late) RAW_BAR();
 
   // CS: this block's turn comes every nbx-th K-tile, starting at its n-tile
   // index; wave-uniform scalars, so the extra MFMAs sit behind scalar tests
@@ -231,14 +283,6 @@ void gemm256_kernel(const bf16_t* __restrict__ A,
 
   bf16x8 af[8][2];
   for (int t = 0; t < nk; ++t) {
-    if (t + 1 == nk && nk > 1) {
-      // last tile: its B q2/q3 units (staged at (t-1).ph0) are the newest
-      // in flight and the counted vmcnt(6) protocol never covers them —
-      // nothing is staged after them to push them past the watermark.
-      // Drain fully once per block before the final tile's reads.
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      RAW_BAR();
-    }
     // ---- phase 0: read ALL A fragments + B fragment 0; stage B(t+1,q23)
     {
       const bf16_t* as0 = aslot + ((4 * t + 2 * wm) & 7) * SLOT_E;
@@ -292,9 +336,24 @@ void gemm256_kernel(const bf16_t* __restrict__ A,
       }
       if (p == 1 && t + 2 < nk) stage_a(t + 2, 0);
       if (p == 2 && t + 2 < nk) stage_a(t + 2, 2);
-      if (p == 3 && t + 2 < nk) stage_b(t + 2, 0);
+      if (p == 3) {
+        // tile boundary, in front of the phase's first barrier (RAW rule of
+        // the header): past vmcnt(6) only A(t+2) and B(t+2,q01) are in
+        // flight, tile t+1 is whole. Tile nk-2 has nothing to stage and
+        // drains B(nk-1,q23), which no later stage would push past a count.
+        if (t + 2 < nk) {
+          stage_b(t + 2, 0);
+          VMCNT6();
+        } else {
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        // WAR rule: B(t,q3) is restaged one phase on, so these reads retire
+        // before the barrier, in both layouts
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+      }
       RAW_BAR();
-      LGKM_WAIT_KO();
+      if (p != 3) LGKM_WAIT_KO();
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int mi = 0; mi < 8; ++mi)
@@ -303,10 +362,10 @@ void gemm256_kernel(const bf16_t* __restrict__ A,
           acc[mi][p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
               af[mi][kk], bfp[kk], acc[mi][p], 0, 0, 0);
       __builtin_amdgcn_s_setprio(0);
-      if (p == 3) VMCNT6();  // tile boundary: t+1 fully resident
       RAW_BAR();
     }
   }
+  if (!late) RAW_BAR();  // waves 0..3 wait out the late half's last cluster
 
   // ---- column sums: all 16 result columns are equal, the lanes of column
   // 0 store rows 4*(lane>>4) + e of m-fragments 2wn, 2wn+1

@@ -290,9 +290,10 @@ def mlp_bwd(dy, x, w1, w2, h, pre):
         w2T = transpose2d(w2)                       # [4d, d] KC
         dh, _ = _gemm_raw(dy, w2T, True, True, M, K2, N2, N2, N2, 0, 0, 1,
                           epi=4, out_pre=pre)
-        db1 = _bias_sum(dh)
         dw2, db2 = wgrad(dy, h, True)
-        dx, dw1, _ = linear_bwd(dh, x, w1, False, "none", None)
+        # db1 = column sums of dh: from the in-place wgrad's fragments where
+        # linear_bwd takes that branch, its streaming _bias_sum elsewhere
+        dx, dw1, db1 = linear_bwd(dh, x, w1, True, "none", None)
         out["r"] = (dx, dw1, db1, dw2, db2)
 
     def _base():
