@@ -20,7 +20,13 @@ rotates q and the new K row at the device position, appends and attends
 with each K/V row read once per query group. "auto" fuses every group
 size the kernel covers (FUSED_GROUPS): measured 4-10x faster per call than
 the composed GQA step at every (D, G), 2.1x decode tokens/s on
-llama-1b-gqa (docs/KERNELS.md "Decode attention: GQA + RoPE")."""
+llama-1b-gqa (docs/KERNELS.md "Decode attention: GQA + RoPE").
+
+Sampling (temperature > 0, top-k, top-p): generate(..., sampler=) or
+TEPDIST_SAMPLER picks "host" (default: softmax on the device, draw on the
+CPU, eager loop), "device" (ops.sample_logits, which on the GPU keeps the
+sampled step inside the captured decode graph) or "auto"
+(docs/KERNELS.md "Sampling")."""
 
 from __future__ import annotations
 
@@ -232,7 +238,22 @@ class Generator:
             x = self._llama_mlp(x, blk)
         return x
 
-    def _decode_step_llama(self, tok, cur_t, kc, vc, kpos):
+    def _emit(self, x, tok, cur_t, sample):
+        """Tail of a static decode step: the next token into tok, cur_t
+        advanced. sample None = greedy; else the sample_logits keywords,
+        and the token is drawn on the device at the position it is written
+        to (cur_t after the increment), straight from the head's output:
+        no fp32 copy, no slice, nothing read back."""
+        if sample is None:
+            logits = self._logits(x).float()[:, -1, :self.cfg.vocab_size]
+            tok.copy_(logits.argmax(-1, keepdim=True))
+            cur_t.add_(1)
+            return
+        cur_t.add_(1)
+        ops.sample_logits(self._logits(x)[:, -1], vocab=self.cfg.vocab_size,
+                          step=cur_t, out=tok, **sample)
+
+    def _decode_step_llama(self, tok, cur_t, kc, vc, kpos, sample=None):
         cfg = self.cfg
         B = tok.shape[0]
         H, Hkv, d = cfg.n_head, self.kv_heads, cfg.n_embd
@@ -259,9 +280,7 @@ class Generator:
                 a = a.transpose(1, 2)
             x = x + ops.linear(a.reshape(B, d), blk.w_o).reshape(B, 1, d)
             x = self._llama_mlp(x, blk)
-        logits = self._logits(x).float()[:, -1, :cfg.vocab_size]
-        tok.copy_(logits.argmax(-1, keepdim=True))
-        cur_t.add_(1)
+        self._emit(x, tok, cur_t, sample)
 
     # -- static-shape greedy decode step (hipGraph-capturable) -----------
     #
@@ -273,9 +292,9 @@ class Generator:
     # slicing), argmaxes, feeds the next token back into tok, and
     # advances cur_t — so a captured graph replays autonomously.
 
-    def _decode_step(self, tok, cur_t, kc, vc, kpos):
+    def _decode_step(self, tok, cur_t, kc, vc, kpos, sample=None):
         if self.llama:
-            return self._decode_step_llama(tok, cur_t, kc, vc, kpos)
+            return self._decode_step_llama(tok, cur_t, kc, vc, kpos, sample)
         cfg = self.cfg
         B = tok.shape[0]
         H, d = cfg.n_head, self.m.wte.shape[1]
@@ -313,15 +332,51 @@ class Generator:
             h = ops.layernorm(x, blk.ln2_g, blk.ln2_b, cfg.ln_eps)
             h = ops.linear(h, blk.w_fc, blk.b_fc, act="gelu")
             x = x + ops.linear(h, blk.w_out, blk.b_out)
-        logits = self._logits(x).float()[:, -1, :cfg.vocab_size]
-        tok.copy_(logits.argmax(-1, keepdim=True))
-        cur_t.add_(1)
+        self._emit(x, tok, cur_t, sample)
+
+    def _host_token(self, x, temperature, top_k, top_p, gen):
+        """Greedy, or the host sampler: filters and softmax where the
+        logits live, torch.multinomial on the CPU."""
+        logits = self._logits(x).float()[:, -1]       # [B, V]
+        logits = logits[:, :self.cfg.vocab_size]       # drop pad rows
+        if not temperature > 0:
+            return logits.argmax(-1, keepdim=True)
+        logits = logits / temperature
+        if top_k > 0:
+            kth = logits.topk(top_k, dim=-1).values[:, -1:]
+            logits = logits.masked_fill(logits < kth, float("-inf"))
+        probs = torch.softmax(logits, dim=-1)
+        if top_p < 1.0:
+            # keep the most probable tokens up to the first whose running
+            # mass reaches top_p, its ties included
+            sp = probs.sort(dim=-1, descending=True).values
+            n = (sp.cumsum(-1) < top_p).sum(-1, keepdim=True)
+            thr = sp.gather(-1, n.clamp(max=sp.shape[-1] - 1))
+            probs = probs.masked_fill(probs < thr, 0.0)
+        return torch.multinomial(probs.cpu(), 1,
+                                 generator=gen).to(logits.device)
 
     @torch.no_grad()
     def generate(self, ids: torch.Tensor, max_new_tokens: int,
                  temperature: float = 0.0, top_k: int = 0,
-                 seed: int = 0) -> torch.Tensor:
+                 seed: int = 0, top_p: float = 1.0,
+                 sampler: Optional[str] = None) -> torch.Tensor:
+        """top_p: nucleus sampling on what top-k left (1.0 = off). sampler
+        (else TEPDIST_SAMPLER, else "host") says where temperature > 0
+        draws: "host" = softmax on the device, torch.multinomial on the
+        CPU from torch.Generator(seed), one [B, V] copy and one sync per
+        token; "device" = ops.sample_logits, drawn from Philox(seed, row,
+        position), which on the GPU keeps sampling inside the captured
+        decode graph like greedy; "auto" = device on the GPU for fp32/bf16
+        models, host otherwise. The two samplers draw different (equally
+        valid) tokens for the same seed, so the default stays "host"."""
         cfg = self.cfg
+        if sampler is None:
+            sampler = os.environ.get("TEPDIST_SAMPLER", "host")
+        if sampler not in ("host", "device", "auto"):
+            raise ValueError(
+                f"sampler must be 'host', 'device' or 'auto', "
+                f"got {sampler!r}")
         B, S0 = ids.shape
         H, d = cfg.n_head, cfg.n_embd
         D = d // H
@@ -332,7 +387,16 @@ class Generator:
               for _ in range(cfg.n_layer)]
         vc = [torch.zeros(B, self.kv_heads, S_max, D, dtype=dt, device=dev)
               for _ in range(cfg.n_layer)]
-        gen = torch.Generator(device="cpu").manual_seed(seed)
+        if sampler == "auto":
+            sampler = "device" if ids.is_cuda and dt in (
+                torch.float32, torch.bfloat16) else "host"
+        # sample_logits keywords when tokens are drawn on the device
+        sample = None
+        if temperature > 0 and sampler == "device":
+            sample = dict(temperature=temperature, top_k=top_k, top_p=top_p,
+                          seed=seed)
+        else:
+            gen = torch.Generator(device="cpu").manual_seed(seed)
 
         out = ids
         pos_ids = torch.arange(S0, device=dev)
@@ -340,17 +404,23 @@ class Generator:
         x = self._stack(x, kc, vc, 0)
         cur = S0
 
-        # greedy decode on GPU: static-buffer steps, hipGraph-captured
-        # after two eager warmups (the eager per-token loop is
-        # launch-bound; replaying one recorded step removes ~1000
+        # greedy or device-sampled decode on GPU: static-buffer steps,
+        # hipGraph-captured after two eager warmups (the eager per-token
+        # loop is launch-bound; replaying one recorded step removes ~1000
         # launches/token). TEPDIST_DECODE_GRAPH=0 forces eager.
-        if (temperature == 0 and ids.is_cuda and S_max > S0
+        if ((temperature == 0 or sample is not None) and ids.is_cuda
+                and S_max > S0
                 and max_new_tokens >= 8
                 and os.environ.get("TEPDIST_DECODE_GRAPH", "1") != "0"):
-            logits = self._logits(x).float()[:, -1, :cfg.vocab_size]
-            tok = logits.argmax(-1, keepdim=True)
-            outs = [tok.clone()]
             cur_t = torch.full((1,), S0, device=dev, dtype=torch.long)
+            if sample is None:
+                logits = self._logits(x).float()[:, -1, :cfg.vocab_size]
+                tok = logits.argmax(-1, keepdim=True)
+            else:
+                tok = ops.sample_logits(self._logits(x)[:, -1],
+                                        vocab=cfg.vocab_size, step=cur_t,
+                                        **sample)
+            outs = [tok.clone()]
             kpos = torch.arange(S_max, device=dev)
             n_rest = min(max_new_tokens, S_max - S0) - 1
             graph = None
@@ -360,41 +430,36 @@ class Generator:
                 side.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(side):
                     for _ in range(min(2, n_rest)):
-                        self._decode_step(tok, cur_t, kc, vc, kpos)
+                        self._decode_step(tok, cur_t, kc, vc, kpos, sample)
                         outs.append(tok.clone())
                         done += 1
                 torch.cuda.current_stream().wait_stream(side)
                 if done < n_rest:
                     graph = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(graph):
-                        self._decode_step(tok, cur_t, kc, vc, kpos)
+                        self._decode_step(tok, cur_t, kc, vc, kpos, sample)
             except Exception:
                 graph = None           # capture failed: stay eager
             while done < n_rest:
                 if graph is not None:
                     graph.replay()
                 else:
-                    self._decode_step(tok, cur_t, kc, vc, kpos)
+                    self._decode_step(tok, cur_t, kc, vc, kpos, sample)
                 outs.append(tok.clone())
                 done += 1
             return torch.cat([ids] + outs, dim=1)
         for _ in range(max_new_tokens):
             if cur >= S_max:
                 break
-            logits = self._logits(x).float()[:, -1]       # [B, V]
-            logits = logits[:, :cfg.vocab_size]            # drop pad rows
-            if temperature > 0:
-                logits = logits / temperature
-                if top_k > 0:
-                    kth = logits.topk(top_k, dim=-1).values[:, -1:]
-                    logits = logits.masked_fill(logits < kth, float("-inf"))
-                probs = torch.softmax(logits, dim=-1)
-                nxt = torch.multinomial(probs.cpu(), 1,
-                                        generator=gen).to(dev)
-            else:
-                nxt = logits.argmax(-1, keepdim=True)
-            out = torch.cat([out, nxt], dim=1)
             pos = torch.full((1,), cur, device=dev, dtype=torch.long)
+            if sample is not None:
+                # drawn where the logits live, at the position written to
+                nxt = ops.sample_logits(self._logits(x)[:, -1],
+                                        vocab=cfg.vocab_size, step=pos,
+                                        **sample)
+            else:
+                nxt = self._host_token(x, temperature, top_k, top_p, gen)
+            out = torch.cat([out, nxt], dim=1)
             x = self._embed(nxt, pos)
             x = self._stack(x, kc, vc, cur)
             cur += 1

@@ -9,6 +9,7 @@ from tepdist_amd.ops.interface import (  # noqa: F401
     attention,
     attention_qkv,
     decode_attention,
+    sample_logits,
     MoERoute,
     moe_route,
     moe_dispatch,

@@ -27,6 +27,7 @@ SOURCES = [
     "gemm256.hip",
     "attention.hip",
     "decode_attention.hip",
+    "sampling.hip",
     "moe_route.hip",
     "transpose.hip",
     "layernorm.hip",

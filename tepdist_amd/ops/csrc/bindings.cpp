@@ -189,6 +189,20 @@ PYBIND11_MODULE(_tepdist_hip, m) {
     check_launch();
   });
 
+  m.def("sample_logits", [](uintptr_t logits, bool logits_bf16,
+                            int64_t row_stride, int B, int vocab,
+                            float temperature, int top_k, float top_p,
+                            uint64_t seed, uintptr_t step, uintptr_t u,
+                            uintptr_t out, uintptr_t tau, uintptr_t stream) {
+    sample_logits(reinterpret_cast<const void*>(logits), logits_bf16,
+                  row_stride, B, vocab, temperature, top_k, top_p, seed,
+                  reinterpret_cast<const int64_t*>(step),
+                  reinterpret_cast<const float*>(u),
+                  reinterpret_cast<int64_t*>(out),
+                  reinterpret_cast<float*>(tau), S(stream));
+    check_launch();
+  });
+
   m.def("moe_route_ws_ints", &moe_route_ws_ints);
 
   m.def("moe_route", [](uintptr_t gates, bool gates_fp32, uintptr_t topi,

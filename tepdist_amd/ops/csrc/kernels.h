@@ -132,6 +132,24 @@ void decode_attention_bf16(const void* q, const void* k_new,
                            int64_t c_bs, int64_t c_hs, int64_t c_rs,
                            hipStream_t stream);
 
+// --- Token sampling (sampling.hip) -----------------------------------------
+// out[b] (int64 [B]) := one token of row b of logits [B, >= vocab] (fp32, or
+// bf16 when logits_bf16; columns contiguous, rows row_stride elements
+// apart, any alignment), drawn from softmax(z / temperature) over columns
+// < vocab after top-k (0 or >= vocab: off; ties at the k-th value kept) and
+// top-p (>= 1: off) by inverse CDF in index order. The uniform is u[b]
+// (fp32) or, when u is null, the first word of Philox4(seed, b, step[0]);
+// exactly one of u and step is given. tau (fp32 [B], may be null) receives
+// the final threshold: columns with z >= tau were kept. Always
+// 0 <= out[b] < vocab. One workgroup per row, no workspace, no host sync;
+// vocab <= 2^22 keeps every 64-bit sum of the 2^40-scaled weights below
+// 2^62; temperature <= 0, top_p <= 0 or vocab > 2^22 throws.
+void sample_logits(const void* logits, bool logits_bf16, int64_t row_stride,
+                   int B, int vocab, float temperature, int top_k,
+                   float top_p, uint64_t seed, const int64_t* step,
+                   const float* u, int64_t* out, float* tau,
+                   hipStream_t stream);
+
 // --- MoE routing / dispatch / combine (moe_route.hip) ----------------------
 // All maps are int32. gates [T,E] contiguous (bf16, or fp32 when
 // gates_fp32), 2 <= E <= 64, 1 <= k <= min(4,E), C >= 1, T*k < 2^31,

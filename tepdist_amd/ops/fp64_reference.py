@@ -433,3 +433,38 @@ def dropout_apply(x, mask, p: float):
     y = (x.detach().cpu().float() * float(scale)).to(BF16)
     keep = torch.as_tensor(np.asarray(mask)).reshape(x.shape).bool()
     return torch.where(keep, y, torch.zeros_like(y))
+
+
+# --------------------------------------------------------------------------
+# Token sampling
+# --------------------------------------------------------------------------
+
+def sample_uniform(seed: int, B: int, step: int) -> np.ndarray:
+    """The fp32 uniforms (0, 1] sample_logits draws for rows 0..B-1 at
+    position `step`: first word of Philox4x32-10 with key = (seed lo, seed
+    hi) and counter = (step lo, step hi, b lo, b hi), as Philox4(seed,
+    subseq = b, offset = step) of csrc/common.h, through u32_to_uniform."""
+    rows = np.arange(B, dtype=np.uint64)
+    off = np.uint64(step & 0xFFFFFFFFFFFFFFFF)
+    full = np.full_like(rows, 1)
+    x = philox4x32_10(
+        (full * (off & _M32), full * (off >> np.uint64(32)),
+         rows & _M32, rows >> np.uint64(32)),
+        (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF))[0]
+    return (x >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24) \
+        + np.float32(2.0 ** -25)
+
+
+def sample_probs(z, temperature: float, tau=None) -> np.ndarray:
+    """fp64 probabilities of one row of logits z [V] under sample_logits'
+    rules: p_i proportional to exp((z_i - m) / T) over the kept set
+    z >= tau (everything when tau is None), exactly 1 weight at z_i == m,
+    0 outside the kept set and at -inf."""
+    z = np.asarray(z, dtype=np.float64)
+    m = z.max()
+    with np.errstate(invalid="ignore", over="ignore"):
+        w = np.exp((z - m) / float(temperature))
+    w = np.where(z == m, 1.0, w)
+    if tau is not None:
+        w = np.where(z >= float(tau), w, 0.0)
+    return w / w.sum()

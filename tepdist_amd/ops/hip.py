@@ -815,6 +815,33 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
     return out
 
 
+def sample_logits(logits: torch.Tensor, temperature: float, top_k: int = 0,
+                  top_p: float = 1.0, seed: int = 0,
+                  step: Optional[torch.Tensor] = None,
+                  u: Optional[torch.Tensor] = None,
+                  vocab: Optional[int] = None,
+                  out: Optional[torch.Tensor] = None,
+                  return_threshold: bool = False):
+    """One token per row of logits [B, Vs] (sampling.hip), the rules of
+    reference.sample_logits. One launch on the current stream, no
+    workspace, nothing read back: `step` stays on the device, so a captured
+    launch draws a fresh uniform at every replay. fp32 and bf16 rows of any
+    row stride and alignment are read in place."""
+    from tepdist_amd.ops.reference import sample_check
+    B, vocab = sample_check(logits, temperature, top_k, top_p, step, u,
+                            vocab, out)
+    if out is None:
+        out = torch.empty(B, 1, dtype=torch.int64, device=logits.device)
+    tau = torch.empty(B, dtype=torch.float32, device=logits.device) \
+        if return_threshold else None
+    ext.sample_logits(logits.data_ptr(), logits.dtype == BF16,
+                      logits.stride(0), B, vocab, float(temperature),
+                      int(top_k), min(float(top_p), 1.0),
+                      int(seed) & 0xFFFFFFFFFFFFFFFF, _p(step), _p(u),
+                      out.data_ptr(), _p(tau), _stream())
+    return (out, tau) if return_threshold else out
+
+
 def _packed_dims(name: str, qkv: torch.Tensor, heads: int):
     """(B, S, D) of a packed qkv [B, S, 3*heads*D]; anything that does not
     split that way is refused (the launch would take D = d // heads and

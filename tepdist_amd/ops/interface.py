@@ -296,6 +296,29 @@ def decode_attention(q, k_cache, v_cache, positions, k_new=None, v_new=None,
                                scale, splits, rope_theta)
 
 
+def sample_logits(logits, *, temperature: float, top_k: int = 0,
+                  top_p: float = 1.0, seed: int = 0, step=None, u=None,
+                  vocab: Optional[int] = None, out=None,
+                  return_threshold: bool = False):
+    """One sampled token per row: int64 [B, 1] (inference only, no
+    autograd). logits [B, Vs] fp32 or bf16, last dim contiguous, any row
+    stride; only columns < vocab (default Vs) take part. temperature > 0.
+    top_k: keep the top_k largest logits, ties at the k-th value included
+    (0 or >= vocab: off). top_p: of what top-k left, keep the smallest set
+    of largest logits holding >= top_p of the mass (>= 1: off). The token
+    is drawn by inverse CDF in index order from `u` (fp32 [B]) or, with
+    `step` (int64 [1] on the logits' device, read on the device), from the
+    first Philox4x32-10 word of (seed, row, step): the same on CPU and GPU,
+    for any batch size, in a graph or out of one. `out` (int64 [B, 1]) is
+    written in place and returned. return_threshold: also returns the
+    final threshold tau (fp32 [B]): logits >= tau were kept. The token is
+    always in [0, vocab). The rules in full: ops/reference.py."""
+    assert not logits.requires_grad, "sample_logits has no backward"
+    return _backend(logits).sample_logits(
+        logits, temperature, top_k, top_p, seed, step, u, vocab, out,
+        return_threshold)
+
+
 # --------------------------------------------------------------------------
 # MoE routing / dispatch / combine
 # --------------------------------------------------------------------------

@@ -524,3 +524,126 @@ def moe_combine_bwd(dout: torch.Tensor, y: torch.Tensor, w: torch.Tensor,
     dw = (y[sl.clamp_min(0)].to(acc) * dout.to(acc).unsqueeze(1)).sum(-1)
     dw = torch.where(sl >= 0, dw, torch.zeros_like(dw))
     return dy.to(y.dtype), dw.to(w.dtype)
+
+
+# --------------------------------------------------------------------------
+# Token sampling: temperature, top-k, top-p, inverse-CDF draw
+# --------------------------------------------------------------------------
+#
+# The rules (also the HIP kernel's, csrc/sampling.hip):
+#   1. top-k: tau_k = the top_k-th largest logit; z >= tau_k is kept (ties
+#      at the threshold included). top_k == 0 or >= vocab: no filter.
+#   2. w_i = exp2((z_i - m) * fp32(log2(e) / T)) in fp32, m the row maximum;
+#      exactly 1 at z_i == m and exactly 0 at -inf. Each weight becomes the
+#      integer q_i = trunc(w_i * 2^40) and every sum below is an integer
+#      sum: exact, the same in any order, monotone along the row.
+#   3. top-p acts on what top-k left: tau_p = the largest input value whose
+#      kept tokens z >= tau_p weigh >= ceil(fp32(top_p) * W_k), W_k the
+#      kept total. top_p >= 1: no filter. tau = max(tau_k, tau_p); with no
+#      filter tau is the row minimum.
+#   4. the token is the smallest index whose running sum of kept q reaches
+#      ceil(u * W) clamped to [1, W] (W the final kept total), else the
+#      last kept index; clamped to [0, vocab).
+#   5. u is given, or u_b = (x >> 8) * 2^-24 + 2^-25 with x the first word
+#      of Philox4x32-10(key = seed, counter = (step, b)); clamped to
+#      [2^-25, 1].
+
+_LOG2E = 1.4426950408889634
+SAMPLE_FIX_BITS = 40
+SAMPLE_MAX_VOCAB = 1 << 22      # vocab * 2^40 stays below 2^62
+
+
+def sample_check(logits, temperature, top_k, top_p, step, u, vocab, out):
+    """Argument checks of sample_logits, shared by both backends; returns
+    (B, vocab). Raises ValueError before anything is launched."""
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError("sample_logits: logits must be [B, V], B, V >= 1")
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("sample_logits: logits must be fp32 or bf16, got "
+                         f"{logits.dtype}")
+    B, Vs = logits.shape
+    if Vs > 1 and logits.stride(1) != 1:
+        raise ValueError("sample_logits: the last dim must be contiguous")
+    vocab = Vs if vocab is None else int(vocab)
+    if not 1 <= vocab <= Vs:
+        raise ValueError(f"sample_logits: vocab {vocab} not in [1, {Vs}]")
+    if vocab > SAMPLE_MAX_VOCAB:
+        raise ValueError(f"sample_logits: vocab {vocab} > 2^22 (the 64-bit "
+                         "sums of 2^40-scaled weights would overflow)")
+    if not temperature > 0:
+        raise ValueError("sample_logits: temperature must be > 0 (greedy "
+                         "decoding is argmax, not this op)")
+    if top_k < 0 or not top_p > 0:
+        raise ValueError("sample_logits: top_k >= 0 and top_p > 0")
+    if (u is None) == (step is None):
+        raise ValueError("sample_logits: give exactly one of u and step")
+    if u is not None and (u.dtype != torch.float32 or u.device != logits.device
+                          or tuple(u.shape) != (B,)):
+        raise ValueError("sample_logits: u must be fp32 [B] on the logits' "
+                         "device")
+    if step is not None and (step.dtype != torch.int64 or step.numel() != 1
+                             or step.device != logits.device):
+        raise ValueError("sample_logits: step must be an int64 tensor with "
+                         "one element on the logits' device")
+    if out is not None and (out.dtype != torch.int64
+                            or tuple(out.shape) != (B, 1)
+                            or out.device != logits.device
+                            or not out.is_contiguous()):
+        raise ValueError("sample_logits: out must be a contiguous int64 "
+                         "[B, 1] on the logits' device")
+    return B, vocab
+
+
+def sample_logits(logits: torch.Tensor, temperature: float, top_k: int = 0,
+                  top_p: float = 1.0, seed: int = 0,
+                  step: Optional[torch.Tensor] = None,
+                  u: Optional[torch.Tensor] = None,
+                  vocab: Optional[int] = None,
+                  out: Optional[torch.Tensor] = None,
+                  return_threshold: bool = False):
+    B, vocab = sample_check(logits, temperature, top_k, top_p, step, u,
+                            vocab, out)
+    f32 = torch.float32
+    z = logits[:, :vocab].float()
+    z = torch.where(z == 0, torch.zeros_like(z), z)          # -0 -> +0
+    if u is None:
+        from tepdist_amd.ops.fp64_reference import sample_uniform
+        u = torch.from_numpy(sample_uniform(
+            seed, B, int(step.reshape(-1)[0]))).to(z.device)
+    u = torch.nan_to_num(u.float(), nan=0.0).clamp(2.0 ** -25, 1.0)
+    t32 = torch.tensor(temperature, dtype=f32).item()
+    c = torch.tensor(_LOG2E / t32, dtype=f32)
+    m = torch.where(torch.isnan(z), torch.full_like(z, float("-inf")),
+                    z).amax(-1, keepdim=True)
+    w = torch.exp2((z - m) * c)
+    w = torch.where(z == m, torch.ones_like(w), w)
+    w = torch.where(w >= 0, w.clamp(max=1.0), torch.zeros_like(w))
+    q = (w.double() * float(2 ** SAMPLE_FIX_BITS)).long()
+    zero = torch.zeros_like(q)
+    tau = z.amin(-1)
+    if 0 < top_k < vocab:
+        tau = z.topk(top_k, dim=-1).values[:, -1]
+        q = torch.where(z >= tau[:, None], q, zero)
+    p32 = torch.tensor(min(top_p, 1.0), dtype=f32).double()
+    if p32 < 1.0:
+        Wk = q.sum(-1)
+        t = torch.minimum(torch.ceil(p32 * Wk.double()).long(),
+                          Wk).clamp(min=1)
+        zs, idx = z.sort(dim=-1, descending=True, stable=True)
+        cum = q.gather(-1, idx).cumsum(-1)
+        pos = (cum < t[:, None]).sum(-1)
+        tau_p = zs.gather(-1, pos.clamp(max=vocab - 1)[:, None])[:, 0]
+        tau = torch.where((pos < vocab) & (Wk > 0), tau_p, tau)
+        q = torch.where(z >= tau[:, None], q, zero)
+    cum = q.cumsum(-1)
+    W = cum[:, -1]
+    tq = torch.minimum(torch.ceil(u.double() * W.double()).long(),
+                       W).clamp(min=1)
+    tok = (cum < tq[:, None]).sum(-1)
+    kept = z >= tau[:, None]
+    last = (kept * torch.arange(vocab, device=z.device)).amax(-1)
+    tok = torch.where(tok < vocab, tok, last).clamp(0, vocab - 1)[:, None]
+    if out is not None:
+        out.copy_(tok)
+        tok = out
+    return (tok, tau) if return_threshold else tok
