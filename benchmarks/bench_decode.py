@@ -1,14 +1,17 @@
 """Serving-path benchmark: prefill + decode throughput of the KV-cache
 generation engine (inference/engine.py) on one GPU. Prints one JSON line
 per run: prefill tokens/s and steady-state decode tokens/s, with the
-decode-attention mode in use (TEPDIST_DECODE_ATTN=fused|composed|auto).
+decode-attention mode in use (TEPDIST_DECODE_ATTN=fused|composed|auto) and
+the decode-linear mode (TEPDIST_DECODE_LINEAR=gemm|skinny|auto).
 
     bench_decode.py [config] [mode ...]
 
 config is a GPT-2 or Llama config name (e.g. gpt2-345m, llama-1b-gqa).
 With modes given (e.g. `fused composed fused composed`) the model is built
 once and the modes are measured in that order in this process, which is how
-to compare them: alternating, in one GPU visit."""
+to compare them: alternating, in one GPU visit. A mode is `attn` or
+`attn:linear` (e.g. `auto:gemm auto:auto auto:gemm auto:auto`); a part left
+out or empty keeps the environment's choice."""
 import json
 import os
 import sys
@@ -35,7 +38,8 @@ def build_model(name):
 
 
 def measure(cfg, m, name, mode=None, batch=32, prompt=512, new=128):
-    g = Generator(m, decode_attn=mode)
+    attn, _, lin = (mode or "").partition(":")
+    g = Generator(m, decode_attn=attn or None, decode_linear=lin or None)
     gen = torch.Generator().manual_seed(0)
     ids = torch.randint(0, cfg.vocab_size, (batch, prompt),
                         generator=gen).cuda()
@@ -58,6 +62,7 @@ def measure(cfg, m, name, mode=None, batch=32, prompt=512, new=128):
         "bench": "decode", "config": name, "batch": batch,
         "prompt": prompt, "new_tokens": n_new, "dtype": "bf16",
         "decode_attn": g.decode_attn,
+        "decode_linear": g.decode_linear,
         "decode_attn_fused": g._fused_decode(
             out.new_empty(0, dtype=torch.bfloat16),
             cfg.n_embd // cfg.n_head, cfg.n_head // g.kv_heads),

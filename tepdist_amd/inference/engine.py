@@ -26,7 +26,16 @@ Sampling (temperature > 0, top-k, top-p): generate(..., sampler=) or
 TEPDIST_SAMPLER picks "host" (default: softmax on the device, draw on the
 CPU, eager loop), "device" (ops.sample_logits, which on the GPU keeps the
 sampled step inside the captured decode graph) or "auto"
-(docs/KERNELS.md "Sampling")."""
+(docs/KERNELS.md "Sampling").
+
+Decode-step linears (decode_linear=, or TEPDIST_DECODE_LINEAR): "gemm"
+(default) = ops.linear at every site, as before; "skinny" = every
+single-token linear runs ops.linear_decode / ops.swiglu_linear_decode (the
+skinny weight-streaming kernel, with the residual add, bias + gelu and
+SwiGLU folded into its epilogue) and a site the kernel does not cover
+raises; "auto" = the same at the sites the kernel covers and measured
+faster than the library (hip.skinny_auto), ops.linear elsewhere
+(docs/KERNELS.md "Decode linears"). Prefill is untouched."""
 
 from __future__ import annotations
 
@@ -46,7 +55,8 @@ FUSED_GROUPS = (1, 2, 4, 8)
 
 class Generator:
     def __init__(self, model, max_seq: Optional[int] = None,
-                 decode_attn: Optional[str] = None):
+                 decode_attn: Optional[str] = None,
+                 decode_linear: Optional[str] = None):
         assert model.env.tp_size == 1, "generation engine: tp=1 layout"
         self.m = model
         self.cfg = model.cfg
@@ -61,6 +71,13 @@ class Generator:
                 f"decode_attn must be 'fused', 'composed' or 'auto', "
                 f"got {decode_attn!r}")
         self.decode_attn = decode_attn
+        if decode_linear is None:
+            decode_linear = os.environ.get("TEPDIST_DECODE_LINEAR", "gemm")
+        if decode_linear not in ("gemm", "skinny", "auto"):
+            raise ValueError(
+                f"decode_linear must be 'gemm', 'skinny' or 'auto', "
+                f"got {decode_linear!r}")
+        self.decode_linear = decode_linear
 
     def _fused_decode(self, x, D, G: int = 1) -> bool:
         """Whether single-token steps on tensors like x run the fused
@@ -75,6 +92,44 @@ class Generator:
             return x.dtype == torch.bfloat16 and D in (64, 128) \
                 and G in FUSED_GROUPS
         return self.decode_attn == "fused"
+
+    def _skinny_site(self, x2, w, bias=None, act="none", residual=None,
+                     w_up=None) -> bool:
+        """Whether a single-token linear site on x2 [M, K] runs the decode
+        ops. "gemm": never. On CUDA the skinny plan decides: a site it does
+        not cover raises under "skinny" and stays on ops.linear under
+        "auto", as does a covered site that hip.skinny_auto leaves out. On CPU only an explicit "skinny" selects the reference op."""
+        if self.decode_linear == "gemm":
+            return False
+        if not x2.is_cuda:
+            return self.decode_linear == "skinny"
+        from tepdist_amd.ops import hip
+        epi = hip.skinny_epi(bias, act, residual)
+        why = hip.skinny_why_not(x2, w, epi, w_up, residual)
+        if not why and self.decode_linear == "auto" and not hip.skinny_auto(
+                x2.shape[0], w.shape[0], w.shape[1], epi, w_up is not None):
+            return False            # covered, but measured no faster
+        if why and self.decode_linear == "skinny":
+            raise ValueError(
+                f"decode_linear='skinny': site x{tuple(x2.shape)} w"
+                f"{tuple(w.shape)} is not covered: {why}")
+        return not why
+
+    def _linear(self, x, w, bias=None, act="none", residual=None,
+                decode=False):
+        """residual + act(x @ w^T + bias) in residual's shape (x's leading
+        dims without one). decode: a single-token site, which may run
+        ops.linear_decode with everything in its epilogue."""
+        if decode:
+            x2 = x.reshape(-1, x.shape[-1])
+            r2 = None if residual is None else \
+                residual.reshape(-1, w.shape[0])
+            if self._skinny_site(x2, w, bias, act, r2):
+                y = ops.linear_decode(x2, w, bias, act, r2)
+                return y.reshape(*x.shape[:-1], w.shape[0]) \
+                    if residual is None else y.reshape(residual.shape)
+        y = ops.linear(x, w, bias, act)
+        return y if residual is None else residual + y.reshape(residual.shape)
 
     # -- one transformer stack pass over new tokens x [B, T, d], with
     # caches kc/vc [L][B, H, S_max, D] filled up to `pos` -----------------
@@ -92,7 +147,7 @@ class Generator:
             pos_t = torch.full((1,), pos, device=x.device, dtype=torch.long)
         for li, blk in enumerate(self.m.blocks):
             h = ops.layernorm(x, blk.ln1_g, blk.ln1_b, cfg.ln_eps)
-            qkv = ops.linear(h, blk.w_qkv, blk.b_qkv)      # [B,T,3d]
+            qkv = self._linear(h, blk.w_qkv, blk.b_qkv, decode=T == 1)
             if fused:
                 # one kernel: cache append at pos + attention over 0..pos,
                 # reading q/k/v as views of the packed projection
@@ -125,18 +180,23 @@ class Generator:
                     p = torch.softmax(scores.float(), dim=-1).to(vall.dtype)
                     a = ops.matmul(p, vall.contiguous())
                 a = a.transpose(1, 2).reshape(B, T, d)
-            x = x + ops.linear(a, blk.w_proj, blk.b_proj)
+            x = self._linear(a, blk.w_proj, blk.b_proj, residual=x,
+                             decode=T == 1)
             h = ops.layernorm(x, blk.ln2_g, blk.ln2_b, cfg.ln_eps)
-            h = ops.linear(h, blk.w_fc, blk.b_fc, act="gelu")
-            x = x + ops.linear(h, blk.w_out, blk.b_out)
+            h = self._linear(h, blk.w_fc, blk.b_fc, act="gelu",
+                             decode=T == 1)
+            x = self._linear(h, blk.w_out, blk.b_out, residual=x,
+                             decode=T == 1)
         return x
 
     def _logits(self, x):
         if self.llama:
             h = ops.rmsnorm(x[:, -1], self.m.ln_f_g, self.cfg.rms_eps)
-            return ops.linear(h, self.m.lm_head)[:, None]   # untied head
+            return self._linear(h, self.m.lm_head,   # untied head
+                                decode=x.shape[1] == 1)[:, None]
         x = ops.layernorm(x, self.m.lnf_g, self.m.lnf_b, self.cfg.ln_eps)
-        return ops.linear(x[:, -1:], self.m.wte)   # last position only
+        return self._linear(x[:, -1:], self.m.wte,   # last position only
+                            decode=x.shape[1] == 1)
 
     def _embed(self, ids, pos_ids):
         """Input embedding of ids [B, T]; pos_ids [T] (or [1]) only feeds
@@ -156,8 +216,12 @@ class Generator:
         cfg = self.cfg
         B, T, d = x.shape
         hn = ops.rmsnorm(x.reshape(B * T, d), blk.ln2_g, cfg.rms_eps)
-        h = ops.swiglu(ops.linear(hn, blk.w_gate), ops.linear(hn, blk.w_up))
-        return x + ops.linear(h, blk.w_down).reshape(B, T, d)
+        if T == 1 and self._skinny_site(hn, blk.w_gate, w_up=blk.w_up):
+            h = ops.swiglu_linear_decode(hn, blk.w_gate, blk.w_up)
+        else:
+            h = ops.swiglu(ops.linear(hn, blk.w_gate),
+                           ops.linear(hn, blk.w_up))
+        return self._linear(h, blk.w_down, residual=x, decode=T == 1)
 
     def _llama_qkv(self, x, blk):
         """Packed projection [B*T, (H + 2 Hkv) D] and its q/k/v views."""
@@ -166,7 +230,7 @@ class Generator:
         H, Hkv = cfg.n_head, self.kv_heads
         D = d // H
         h = ops.rmsnorm(x.reshape(B * T, d), blk.ln1_g, cfg.rms_eps)
-        qkv = ops.linear(h, blk.w_qkv)
+        qkv = self._linear(h, blk.w_qkv, decode=T == 1)
         return (qkv[:, :H * D].view(B, T, H, D),
                 qkv[:, H * D:(H + Hkv) * D].view(B, T, Hkv, D),
                 qkv[:, (H + Hkv) * D:].view(B, T, Hkv, D))
@@ -234,7 +298,8 @@ class Generator:
                     a = self._gqa_attend(qh, kc[li][:, :, :pos + T],
                                          vc[li][:, :, :pos + T], dead)
                 a = a.transpose(1, 2)
-            x = x + ops.linear(a.reshape(B * T, d), blk.w_o).reshape(B, T, d)
+            x = self._linear(a.reshape(B * T, d), blk.w_o, residual=x,
+                             decode=T == 1)
             x = self._llama_mlp(x, blk)
         return x
 
@@ -278,7 +343,8 @@ class Generator:
                 vc[li].index_copy_(2, cur_t, v.transpose(1, 2))
                 a = self._gqa_attend(qh, kc[li], vc[li], dead)
                 a = a.transpose(1, 2)
-            x = x + ops.linear(a.reshape(B, d), blk.w_o).reshape(B, 1, d)
+            x = self._linear(a.reshape(B, d), blk.w_o, residual=x,
+                             decode=True)
             x = self._llama_mlp(x, blk)
         self._emit(x, tok, cur_t, sample)
 
@@ -307,7 +373,7 @@ class Generator:
             mask = (kpos > cur_t)                   # [S_max] device bool
         for li, blk in enumerate(self.m.blocks):
             h = ops.layernorm(x, blk.ln1_g, blk.ln1_b, cfg.ln_eps)
-            qkv = ops.linear(h, blk.w_qkv, blk.b_qkv)
+            qkv = self._linear(h, blk.w_qkv, blk.b_qkv, decode=True)
             if fused:
                 # the kernel reads cur_t on the device: appends k/v at
                 # cur_t and attends rows 0..cur_t only (no S_max sweep)
@@ -328,10 +394,12 @@ class Generator:
                 p = torch.softmax(scores.float(), dim=-1).to(x.dtype)
                 a = ops.matmul(p, vc[li])
                 a = a.transpose(1, 2).reshape(B, 1, d)
-            x = x + ops.linear(a, blk.w_proj, blk.b_proj)
+            x = self._linear(a, blk.w_proj, blk.b_proj, residual=x,
+                             decode=True)
             h = ops.layernorm(x, blk.ln2_g, blk.ln2_b, cfg.ln_eps)
-            h = ops.linear(h, blk.w_fc, blk.b_fc, act="gelu")
-            x = x + ops.linear(h, blk.w_out, blk.b_out)
+            h = self._linear(h, blk.w_fc, blk.b_fc, act="gelu", decode=True)
+            x = self._linear(h, blk.w_out, blk.b_out, residual=x,
+                             decode=True)
         self._emit(x, tok, cur_t, sample)
 
     def _host_token(self, x, temperature, top_k, top_p, gen):

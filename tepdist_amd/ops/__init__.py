@@ -9,6 +9,8 @@ from tepdist_amd.ops.interface import (  # noqa: F401
     attention,
     attention_qkv,
     decode_attention,
+    linear_decode,
+    swiglu_linear_decode,
     sample_logits,
     MoERoute,
     moe_route,

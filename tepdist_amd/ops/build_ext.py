@@ -27,6 +27,7 @@ SOURCES = [
     "gemm256.hip",
     "attention.hip",
     "decode_attention.hip",
+    "skinny_gemm.hip",
     "sampling.hip",
     "moe_route.hip",
     "transpose.hip",
@@ -41,6 +42,20 @@ SOURCES = [
     "debug.hip",
     "bindings.cpp",
 ]
+
+
+# per-source flags. skinny_gemm.hip is built without the packed fp32 VALU
+# forms: without the flag its wave-order LDS sum and epilogue compile to 330
+# v_pk_add/mul/fma_f32 over the nine instantiations (264 of them the sum),
+# with it to none, at identical VGPR, scratch and occupancy figures. The
+# kernel is bandwidth-bound, so the plain forms cost nothing, and the
+# bit-exact sums its tests demand then rest on v_add_f32 / v_fma_f32 alone.
+# -Xclang reaches the host pass too, which has no such feature and ignores
+# it (hipcc's -Xarch_device does not take options with arguments).
+EXTRA_FLAGS = {
+    "skinny_gemm.hip": ["-Xclang", "-target-feature",
+                        "-Xclang", "-packed-fp32-ops"],
+}
 
 
 def _includes():
@@ -59,6 +74,7 @@ def _needs_build() -> bool:
     deps = [CSRC / s for s in SOURCES] + [CSRC / "common.h", CSRC / "kernels.h",
                                           CSRC / "lds_frag.h",
                                           CSRC / "gemm_plan.h",
+                                          CSRC / "skinny_plan.h",
                                           CSRC / "gemm_tile.h",
                                           CSRC / "rope_common.h",
                                           Path(__file__)]
@@ -122,7 +138,7 @@ def build(force: bool = False, verbose: bool = True) -> Path:
     def compile_one(src: str) -> Path:
         obj = BUILD / (src.replace(".", "_") + ".o")
         lang = ["-x", "hip"] if src.endswith(".hip") else []
-        cmd = base + lang + ["-c", str(CSRC / src), "-o", str(obj)]
+        cmd = base + EXTRA_FLAGS.get(src, []) + lang + ["-c", str(CSRC / src), "-o", str(obj)]
         if verbose:
             print("[build_ext]", " ".join(cmd), flush=True)
         r = subprocess.run(cmd, capture_output=True, text=True)

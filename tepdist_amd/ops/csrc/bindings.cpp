@@ -13,6 +13,7 @@
 #include "common.h"
 #include "gemm_plan.h"
 #include "kernels.h"
+#include "skinny_plan.h"
 
 namespace py = pybind11;
 using namespace tepdist;
@@ -69,6 +70,28 @@ PYBIND11_MODULE(_tepdist_hip, m) {
   }, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("lda"),
      py::arg("ldb"), py::arg("a_kc") = true, py::arg("b_kc") = true,
      py::arg("epi") = 0, py::arg("batch") = 1);
+
+  m.def("skinny_gemm", [](uintptr_t x, uintptr_t w, uintptr_t w2,
+                          uintptr_t bias, uintptr_t res, uintptr_t y, int M,
+                          int N, int K, int64_t ldx, int64_t ldw,
+                          int64_t ldw2, int64_t ldr, int64_t ldy, int epi,
+                          uintptr_t stream) {
+    skinny_gemm_bf16(reinterpret_cast<void*>(x), reinterpret_cast<void*>(w),
+                     reinterpret_cast<void*>(w2),
+                     reinterpret_cast<void*>(bias),
+                     reinterpret_cast<void*>(res), reinterpret_cast<void*>(y),
+                     M, N, K, ldx, ldw, ldw2, ldr, ldy, epi, S(stream));
+    check_launch();
+  });
+
+  // (mt, rows, waves, k_per_wave, split_k, why_not) — host-only, no GPU
+  m.def("skinny_plan", [](int M, int N, int K, int64_t ldx, int64_t ldw,
+                          int epi, bool dual) {
+    const SkinnyPlan p = skinny_plan(M, N, K, ldx, ldw, epi, dual);
+    return py::make_tuple(p.mt, p.rows, p.waves, p.k_per_wave, p.split_k,
+                          p.why_not ? p.why_not : "");
+  }, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("ldx"),
+     py::arg("ldw"), py::arg("epi") = 0, py::arg("dual") = false);
 
   m.def("transpose", [](uintptr_t in, uintptr_t out, int R, int C,
                         int64_t si, int64_t so, int batch,

@@ -50,6 +50,19 @@ void gemm256_bf16(const void* A, const void* B, void* C, void* c_pre,
                   int split_k, int k_chunk, float* colsum_parts,
                   hipStream_t stream);
 
+// --- Skinny-M decode linear (skinny_gemm.hip) --------------------------------
+// y[M, N] = epi(x[M, K] @ W[N, K]^T) for 1 <= M <= 64, K % 64 == 0; epi is
+// the SK_* enum of skinny_plan.h (bias [N], res [M, N] with row stride ldr
+// must be given exactly when epi names them). w2 non-null: the dual form
+// y = silu(x @ W^T) * (x @ w2^T), epi 0 only. Row strides in elements; x,
+// W and w2 need 16-byte-aligned bases and rows. One launch, no
+// workspace, no atomics. Throws with skinny_plan()'s reason when the call
+// is not covered.
+void skinny_gemm_bf16(const void* x, const void* w, const void* w2,
+                      const void* bias, const void* res, void* y, int M,
+                      int N, int K, int64_t ldx, int64_t ldw, int64_t ldw2,
+                      int64_t ldr, int64_t ldy, int epi, hipStream_t stream);
+
 // --- Transpose -------------------------------------------------------------
 // out[c][r] = in[r][c] per batch (strides in elements).
 void transpose_bf16(const void* in, void* out, int R, int C,

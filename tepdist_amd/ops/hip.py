@@ -153,6 +153,95 @@ def linear_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor],
     return fn()
 
 
+# Decode-step linears (csrc/skinny_gemm.hip): M = batch rows against a
+# weight streamed once. Coverage and launch shape come from
+# csrc/skinny_plan.h (ext.skinny_plan); a call it does not cover raises with
+# its reason. There is no library fallback here: the engine decides per
+# site whether to come this way (inference/engine.py).
+
+_SK_EPI = {("none", False, False): 0, ("none", True, False): 1,
+           ("gelu", True, False): 2, ("none", False, True): 3,
+           ("none", True, True): 4}
+
+
+def skinny_why_not(x: torch.Tensor, w: torch.Tensor, epi: int = 0,
+                   w_up: Optional[torch.Tensor] = None,
+                   residual: Optional[torch.Tensor] = None) -> str:
+    """'' when skinny_gemm takes this call, else why not."""
+    ts = [t for t in (x, w, w_up, residual) if t is not None]
+    if any(t.dtype != BF16 or t.dim() != 2 or t.stride(1) != 1 for t in ts):
+        return "operands must be 2-D bf16 with a contiguous last dim"
+    M, K = x.shape
+    N = w.shape[0]
+    if w.shape[1] != K or (w_up is not None and w_up.shape != w.shape):
+        return "weight shapes do not match x"
+    if residual is not None and tuple(residual.shape) != (M, N):
+        return "residual must be [M, N]"
+    why = ext.skinny_plan(M, N, K, x.stride(0), w.stride(0), epi,
+                          w_up is not None)[5]
+    if why:
+        return why
+    for t in (x, w, w_up):
+        if t is not None and (t.data_ptr() % 16 or t.stride(0) % 8):
+            return "x and W need 16-byte-aligned bases and rows"
+    return ""
+
+
+def _skinny(x, w, w_up, bias, residual, epi):
+    why = skinny_why_not(x, w, epi, w_up, residual)
+    if why:
+        raise ValueError(f"linear_decode: not covered by the skinny kernel: "
+                         f"{why}")
+    M, K = x.shape
+    N = w.shape[0]
+    if bias is not None:
+        assert bias.dtype == BF16 and bias.shape == (N,)
+        bias = bias.contiguous()
+    y = torch.empty(M, N, dtype=BF16, device=x.device)
+    ext.skinny_gemm(x.data_ptr(), w.data_ptr(), _p(w_up), _p(bias),
+                    _p(residual), y.data_ptr(), M, N, K, x.stride(0),
+                    w.stride(0), w_up.stride(0) if w_up is not None else 0,
+                    residual.stride(0) if residual is not None else 0, N,
+                    epi, _stream())
+    return y
+
+
+def skinny_auto(M: int, N: int, K: int, epi: int, dual: bool) -> bool:
+    """Which covered sites the engine's decode_linear="auto" takes: those
+    where the slowest skinny window beat the fastest hipBLASLt window (plus
+    the launches the epilogue replaces) in profiles/linear_decode.json
+    (docs/KERNELS.md "Decode linears"). The bias + gelu form won at every
+    M, the dual SwiGLU form up to M = 32 (at 64 within the spreads); the
+    others only with one token fragment (M <= 16), below the lm heads' N,
+    and not at every K. Only M in {1, 8, 32, 64} and the flagship shapes
+    were measured: between and beyond them the rule extrapolates."""
+    if epi == 2:
+        return True
+    if dual:
+        return M <= 32
+    if M > 16 or N >= 16384:
+        return False
+    if epi in (3, 4):               # residual epilogues: down (K 6144) lost
+        return K <= 4096
+    return M == 1 or K >= 2048      # plain / bias: K 1024 lost at M = 8
+
+
+def skinny_epi(bias, act: str, residual) -> int:
+    key = (act, bias is not None, residual is not None)
+    if key not in _SK_EPI:
+        raise ValueError(f"linear_decode: no epilogue for act={act!r}, "
+                         f"bias={key[1]}, residual={key[2]}")
+    return _SK_EPI[key]
+
+
+def linear_decode(x, w, bias=None, act: str = "none", residual=None):
+    return _skinny(x, w, None, bias, residual, skinny_epi(bias, act, residual))
+
+
+def swiglu_linear_decode(x, w_gate, w_up):
+    return _skinny(x, w_gate, w_up, None, None, 0)
+
+
 def _bias_sum(t: torch.Tensor) -> torch.Tensor:
     """Column sums of contiguous t [rows, cols] as bf16 [cols] (the bias
     gradient), accumulated in a zeroed fp32 workspace."""

@@ -296,6 +296,35 @@ def decode_attention(q, k_cache, v_cache, positions, k_new=None, v_new=None,
                                scale, splits, rope_theta)
 
 
+def _no_backward(name, *ts):
+    # weights are Parameters: what must not happen is recording a graph
+    assert not torch.is_grad_enabled() or \
+        not any(t is not None and t.requires_grad for t in ts), \
+        f"{name} has no backward: call it under torch.no_grad()"
+
+
+def linear_decode(x, w, bias=None, act: str = "none", residual=None):
+    """Decode-step linear (inference only, no autograd): y = act(x @ w^T +
+    bias) + residual for x [M, K] with 1 <= M <= 64 rows, w [N, K], bias
+    [N], residual [M, N]; act "none" or "gelu" (gelu needs the bias and
+    takes no residual). Everything is applied to the fp32 sum and rounded
+    once. On the GPU this is the skinny weight-streaming kernel: bf16, K a
+    multiple of 64, 16-byte-aligned rows of x and w at any stride (views
+    are read in place); a call it does not cover raises with the reason.
+    Weights are Parameters, so unlike decode_attention this cannot assert
+    on requires_grad alone: call it under torch.no_grad(). With grad mode
+    on and an operand that requires grad it asserts."""
+    _no_backward("linear_decode", x, w, bias, residual)
+    return _backend(x).linear_decode(x, w, bias, act, residual)
+
+
+def swiglu_linear_decode(x, w_gate, w_up):
+    """silu(x @ w_gate^T) * (x @ w_up^T) in one pass over both weights
+    (inference only). Shapes and coverage as linear_decode."""
+    _no_backward("swiglu_linear_decode", x, w_gate, w_up)
+    return _backend(x).swiglu_linear_decode(x, w_gate, w_up)
+
+
 def sample_logits(logits, *, temperature: float, top_k: int = 0,
                   top_p: float = 1.0, seed: int = 0, step=None, u=None,
                   vocab: Optional[int] = None, out=None,

@@ -62,6 +62,36 @@ def matmul(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return (a.float() @ b.float()).to(a.dtype)
 
 
+def linear_decode(x: torch.Tensor, w: torch.Tensor,
+                  bias: Optional[torch.Tensor] = None, act: str = "none",
+                  residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Decode-step linear y = act(x @ w^T + bias) + residual for x [M, K]:
+    fp32 math throughout, one rounding to x's dtype (no rounded
+    pre-activation, unlike linear_fwd: inference keeps none)."""
+    if act not in ("none", "gelu"):
+        raise ValueError(act)
+    if act == "gelu" and (bias is None or residual is not None):
+        raise ValueError("linear_decode: gelu goes with a bias and no "
+                         "residual")
+    y = x.float() @ w.float().t()
+    if bias is not None:
+        y = y + bias.float()
+    if act == "gelu":
+        y = 0.5 * y * (1.0 + torch.tanh(SQRT_2_OVER_PI
+                                        * (y + 0.044715 * y ** 3)))
+    if residual is not None:
+        y = y + residual.float()
+    return y.to(x.dtype)
+
+
+def swiglu_linear_decode(x: torch.Tensor, w_gate: torch.Tensor,
+                         w_up: torch.Tensor) -> torch.Tensor:
+    """silu(x @ w_gate^T) * (x @ w_up^T) in fp32, one rounding."""
+    xf = x.float()
+    g = xf @ w_gate.float().t()
+    return (g * torch.sigmoid(g) * (xf @ w_up.float().t())).to(x.dtype)
+
+
 # --------------------------------------------------------------------------
 # GELU (tanh approximation, as GPT-2 uses)
 # --------------------------------------------------------------------------
