@@ -35,7 +35,21 @@ skinny weight-streaming kernel, with the residual add, bias + gelu and
 SwiGLU folded into its epilogue) and a site the kernel does not cover
 raises; "auto" = the same at the sites the kernel covers and measured
 faster than the library (hip.skinny_auto), ops.linear elsewhere
-(docs/KERNELS.md "Decode linears"). Prefill is untouched."""
+(docs/KERNELS.md "Decode linears"). Prefill is untouched.
+
+Prefill attention (prefill_attn=, or TEPDIST_PREFILL_ATTN): every pass over
+more than one token, the first chunk and a continuation chunk alike.
+"composed" (default) = as before: the first chunk ropes, writes the cache,
+expands K/V to H heads and runs the training flash forward; a continuation
+chunk runs batched matmuls + softmax over the cache. "fused" = one
+ops.prefill_attention per layer on views of the packed projection: it
+rotates q and the chunk's K rows at the device position, appends K/V to the
+cache and attends cache rows 0 .. pos + t with each K/V row staged once per
+query group; a site the kernel does not cover raises. "auto" = fused where
+the kernel covers the call and hip.prefill_auto has it measured ahead,
+composed elsewhere and on CPU (docs/KERNELS.md "Prefill attention over the
+cache"). generate(..., prefill_chunk=c) feeds the prompt in chunks of c
+tokens."""
 
 from __future__ import annotations
 
@@ -56,7 +70,8 @@ FUSED_GROUPS = (1, 2, 4, 8)
 class Generator:
     def __init__(self, model, max_seq: Optional[int] = None,
                  decode_attn: Optional[str] = None,
-                 decode_linear: Optional[str] = None):
+                 decode_linear: Optional[str] = None,
+                 prefill_attn: Optional[str] = None):
         assert model.env.tp_size == 1, "generation engine: tp=1 layout"
         self.m = model
         self.cfg = model.cfg
@@ -78,6 +93,13 @@ class Generator:
                 f"decode_linear must be 'gemm', 'skinny' or 'auto', "
                 f"got {decode_linear!r}")
         self.decode_linear = decode_linear
+        if prefill_attn is None:
+            prefill_attn = os.environ.get("TEPDIST_PREFILL_ATTN", "composed")
+        if prefill_attn not in ("composed", "fused", "auto"):
+            raise ValueError(
+                f"prefill_attn must be 'composed', 'fused' or 'auto', "
+                f"got {prefill_attn!r}")
+        self.prefill_attn = prefill_attn
 
     def _fused_decode(self, x, D, G: int = 1) -> bool:
         """Whether single-token steps on tensors like x run the fused
@@ -92,6 +114,20 @@ class Generator:
             return x.dtype == torch.bfloat16 and D in (64, 128) \
                 and G in FUSED_GROUPS
         return self.decode_attn == "fused"
+
+    def _fused_prefill(self, x, H, Hkv, D) -> bool:
+        """Whether a pass of T > 1 tokens x [B, T, H * D] runs
+        ops.prefill_attention. "fused": always (on the GPU the op raises at
+        a site the kernel does not cover; on CPU it is the reference op).
+        "auto": on the GPU, where the kernel covers the call and
+        hip.prefill_auto has it measured ahead; never on CPU."""
+        if self.prefill_attn != "auto":
+            return self.prefill_attn == "fused"
+        if not x.is_cuda:
+            return False
+        from tepdist_amd.ops import hip
+        return not hip.prefill_why_not(x.dtype, H, Hkv, D) and \
+            hip.prefill_auto(x.shape[0], x.shape[1], Hkv, H // Hkv, D)
 
     def _skinny_site(self, x2, w, bias=None, act="none", residual=None,
                      w_up=None) -> bool:
@@ -143,12 +179,20 @@ class Generator:
         D = d // H
         scale = 1.0 / math.sqrt(D)
         fused = T == 1 and self._fused_decode(x, D)
-        if fused:
+        pf = T > 1 and self._fused_prefill(x, H, H, D)
+        if fused or pf:
             pos_t = torch.full((1,), pos, device=x.device, dtype=torch.long)
         for li, blk in enumerate(self.m.blocks):
             h = ops.layernorm(x, blk.ln1_g, blk.ln1_b, cfg.ln_eps)
             qkv = self._linear(h, blk.w_qkv, blk.b_qkv, decode=T == 1)
-            if fused:
+            if pf:
+                # one op: cache append at pos.. and attention over
+                # 0..pos + t, on views of the packed projection
+                q4 = qkv.view(B, T, 3, H, D)
+                a = ops.prefill_attention(q4[:, :, 0], kc[li], vc[li], pos_t,
+                                          k_new=q4[:, :, 1],
+                                          v_new=q4[:, :, 2]).reshape(B, T, d)
+            elif fused:
                 # one kernel: cache append at pos + attention over 0..pos,
                 # reading q/k/v as views of the packed projection
                 q3 = qkv.view(B, 3, H, D)
@@ -259,8 +303,9 @@ class Generator:
         D, G = d // H, H // Hkv
         theta = cfg.rope_theta
         fused = T == 1 and self._fused_decode(x, D, G)
+        pf = T > 1 and self._fused_prefill(x, H, Hkv, D)
         prefill = T > 1 and pos == 0
-        if fused:
+        if fused or pf:
             pos_t = torch.full((1,), pos, device=x.device, dtype=torch.long)
         elif not prefill:
             qpos = torch.arange(pos, pos + T, device=x.device)
@@ -270,7 +315,12 @@ class Generator:
                 dead = kpos[None, :] > qpos[:, None]
         for li, blk in enumerate(self.m.blocks):
             q, k, v = self._llama_qkv(x, blk)
-            if fused:
+            if pf:
+                # one op: rope of q and the chunk's K rows at pos + t, cache
+                # append, attention over 0..pos + t, K/V read at Hkv heads
+                a = ops.prefill_attention(q, kc[li], vc[li], pos_t, k_new=k,
+                                          v_new=v, rope_theta=theta)
+            elif fused:
                 # one kernel: rope of q and the new K row at pos, cache
                 # append, attention over 0..pos, on views of the projection
                 a = ops.decode_attention(q[:, 0], kc[li], vc[li], pos_t,
@@ -428,8 +478,10 @@ class Generator:
     def generate(self, ids: torch.Tensor, max_new_tokens: int,
                  temperature: float = 0.0, top_k: int = 0,
                  seed: int = 0, top_p: float = 1.0,
-                 sampler: Optional[str] = None) -> torch.Tensor:
-        """top_p: nucleus sampling on what top-k left (1.0 = off). sampler
+                 sampler: Optional[str] = None,
+                 prefill_chunk: Optional[int] = None) -> torch.Tensor:
+        """prefill_chunk: feed the prompt through the stack in chunks of
+        that many tokens (None = one chunk). top_p: nucleus sampling on what top-k left (1.0 = off). sampler
         (else TEPDIST_SAMPLER, else "host") says where temperature > 0
         draws: "host" = softmax on the device, torch.multinomial on the
         CPU from torch.Generator(seed), one [B, V] copy and one sync per
@@ -468,8 +520,17 @@ class Generator:
 
         out = ids
         pos_ids = torch.arange(S0, device=dev)
-        x = self._embed(ids, pos_ids)
-        x = self._stack(x, kc, vc, 0)
+        if prefill_chunk is not None and prefill_chunk < 1:
+            raise ValueError(f"prefill_chunk must be >= 1, "
+                             f"got {prefill_chunk!r}")
+        if prefill_chunk is None or prefill_chunk >= S0:
+            x = self._embed(ids, pos_ids)
+            x = self._stack(x, kc, vc, 0)
+        else:
+            for c0 in range(0, S0, prefill_chunk):
+                c1 = min(c0 + prefill_chunk, S0)
+                x = self._embed(ids[:, c0:c1], pos_ids[c0:c1])
+                x = self._stack(x, kc, vc, c0)
         cur = S0
 
         # greedy or device-sampled decode on GPU: static-buffer steps,

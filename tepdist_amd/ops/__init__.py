@@ -9,6 +9,7 @@ from tepdist_amd.ops.interface import (  # noqa: F401
     attention,
     attention_qkv,
     decode_attention,
+    prefill_attention,
     linear_decode,
     swiglu_linear_decode,
     sample_logits,

@@ -27,6 +27,7 @@ SOURCES = [
     "gemm256.hip",
     "attention.hip",
     "decode_attention.hip",
+    "prefill_attention.hip",
     "skinny_gemm.hip",
     "sampling.hip",
     "moe_route.hip",
@@ -52,9 +53,12 @@ SOURCES = [
 # bit-exact sums its tests demand then rest on v_add_f32 / v_fma_f32 alone.
 # -Xclang reaches the host pass too, which has no such feature and ignores
 # it (hipcc's -Xarch_device does not take options with arguments).
+# prefill_attention.hip takes the same flag: its softmax rescale and
+# epilogue would otherwise pair into v_pk_mul_f32.
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
-    "skinny_gemm.hip": ["-Xclang", "-target-feature",
-                        "-Xclang", "-packed-fp32-ops"],
+    "skinny_gemm.hip": _NO_PK_F32,
+    "prefill_attention.hip": _NO_PK_F32,
 }
 
 

@@ -212,6 +212,27 @@ PYBIND11_MODULE(_tepdist_hip, m) {
     check_launch();
   });
 
+  m.def("prefill_attention", [](uintptr_t q, uintptr_t k_new,
+                                uintptr_t v_new, uintptr_t k_cache,
+                                uintptr_t v_cache, uintptr_t pos,
+                                int pos_stride, uintptr_t out, int B, int T,
+                                int H, int Hkv, int S_max, int D, float scale,
+                                bool rope, float rope_theta, int64_t q_bs,
+                                int64_t q_ts, int64_t q_hs, int64_t n_bs,
+                                int64_t n_ts, int64_t n_hs, int64_t c_bs,
+                                int64_t c_hs, int64_t c_rs,
+                                uintptr_t stream) {
+    prefill_attention_bf16(
+        reinterpret_cast<void*>(q), reinterpret_cast<void*>(k_new),
+        reinterpret_cast<void*>(v_new), reinterpret_cast<void*>(k_cache),
+        reinterpret_cast<void*>(v_cache),
+        reinterpret_cast<const int64_t*>(pos), pos_stride,
+        reinterpret_cast<void*>(out), B, T, H, Hkv, S_max, D, scale, rope,
+        rope_theta, q_bs, q_ts, q_hs, n_bs, n_ts, n_hs, c_bs, c_hs, c_rs,
+        S(stream));
+    check_launch();
+  });
+
   m.def("sample_logits", [](uintptr_t logits, bool logits_bf16,
                             int64_t row_stride, int B, int vocab,
                             float temperature, int top_k, float top_p,

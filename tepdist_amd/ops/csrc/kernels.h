@@ -145,6 +145,28 @@ void decode_attention_bf16(const void* q, const void* k_new,
                            int64_t c_bs, int64_t c_hs, int64_t c_rs,
                            hipStream_t stream);
 
+// --- Prefill attention over a KV cache (prefill_attention.hip) -------------
+// A chunk of T query tokens per batch row against the cache. q: [B,T,H,D]
+// bf16 (q_bs, q_ts, q_hs element strides, D contiguous); k_new/v_new:
+// [B,T,Hkv,D] sharing (n_bs, n_ts, n_hs), both may be null; k/v_cache:
+// [B,Hkv,S_max,D] sharing (c_bs, c_hs, c_rs); out: [B,T,H,D] contiguous.
+// pos: device int64 read at pos[b * pos_stride] (0 or 1), clamped into
+// [0, S_max - T] in the kernels: p0. With new rows, row t is first stored
+// into cache[b,:,p0+t,:] (K rotated at p0 + t and rounded once when rope);
+// then query t attends cache rows 0 .. p0+t of K/V head h / G, G = H / Hkv
+// in {1,2,4,8}. With rope, q is rotated at p0 + t and rounded once to bf16.
+// D in {64,128}, T <= S_max, scale > 0; anything else throws. Two launches
+// (append, attention) on `stream`; no workspace.
+void prefill_attention_bf16(const void* q, const void* k_new,
+                            const void* v_new, void* k_cache, void* v_cache,
+                            const int64_t* pos, int pos_stride, void* out,
+                            int B, int T, int H, int Hkv, int S_max, int D,
+                            float scale, bool rope, float rope_theta,
+                            int64_t q_bs, int64_t q_ts, int64_t q_hs,
+                            int64_t n_bs, int64_t n_ts, int64_t n_hs,
+                            int64_t c_bs, int64_t c_hs, int64_t c_rs,
+                            hipStream_t stream);
+
 // --- Token sampling (sampling.hip) -----------------------------------------
 // out[b] (int64 [B]) := one token of row b of logits [B, >= vocab] (fp32, or
 // bf16 when logits_bf16; columns contiguous, rows row_stride elements

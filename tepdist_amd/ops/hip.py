@@ -904,6 +904,101 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
     return out
 
 
+def prefill_why_not(dtype, H: int, Hkv: int, D: int) -> str:
+    """Why prefill_attention does not cover `dtype` operands with H query
+    heads over Hkv K/V heads of dim D ("" = covered)."""
+    if dtype != BF16:
+        return "hip backend is bf16-only"
+    if D not in (64, 128):
+        return f"head dim {D} not in (64, 128)"
+    if Hkv < 1 or H % Hkv != 0 or H // Hkv not in (1, 2, 4, 8):
+        return (f"{H} query heads over {Hkv} K/V heads: the group size must "
+                "be 1, 2, 4 or 8")
+    return ""
+
+
+def prefill_auto(B: int, T: int, Hkv: int, G: int, D: int) -> bool:
+    """Whether "auto" takes the fused prefill attention for a covered call:
+    the measured rule of docs/KERNELS.md "Prefill attention over the cache"
+    (profiles/prefill_attention.json). The slowest fused window beat the
+    fastest composed one at every shape measured: G in {1, 2, 4, 8}, D in
+    {64, 128}, first chunks (2.5-4.0x) and continuation chunks (2.8-12.7x),
+    grids from 32 to 512 blocks. So every covered call is taken; the
+    arguments are what a narrower rule would need."""
+    return True
+
+
+def prefill_attention(q: torch.Tensor, k_cache: torch.Tensor,
+                      v_cache: torch.Tensor, positions: torch.Tensor,
+                      k_new: Optional[torch.Tensor] = None,
+                      v_new: Optional[torch.Tensor] = None,
+                      scale: Optional[float] = None,
+                      rope_theta: Optional[float] = None) -> torch.Tensor:
+    """Attention of a chunk of T query tokens over a KV cache
+    (prefill_attention.hip). Same semantics as reference.prefill_attention,
+    including the in-place cache write of (k_new, v_new) at the device-side
+    position and the in-kernel rotation of q and k_new. Strided views with
+    D contiguous (e.g. of the packed qkv projection) are read in place."""
+    if q.dim() != 4 or k_cache.dim() != 4:
+        raise ValueError("prefill_attention: q [B,T,H,D], caches "
+                         "[B,Hkv,S_max,D]")
+    B, T, H, D = q.shape
+    Hkv, S_max = k_cache.shape[1], k_cache.shape[2]
+    if k_cache.dtype != BF16 or v_cache.dtype != BF16:
+        raise ValueError("prefill_attention: hip backend is bf16-only")
+    why = prefill_why_not(q.dtype, H, Hkv, D)
+    if why:
+        raise ValueError("prefill_attention: " + why)
+    if (k_new is None) != (v_new is None):
+        raise ValueError("prefill_attention: k_new and v_new go together")
+    if T < 1 or T > S_max:
+        raise ValueError(f"prefill_attention: chunk of {T} tokens does not "
+                         f"fit a cache of {S_max} rows")
+    if tuple(k_cache.shape) != (B, Hkv, S_max, D) or \
+            v_cache.shape != k_cache.shape or \
+            v_cache.stride() != k_cache.stride():
+        raise ValueError("prefill_attention: k_cache/v_cache must be "
+                         "[B,Hkv,S_max,D] with equal strides")
+    if q.stride(3) != 1 or k_cache.stride(3) != 1:
+        raise ValueError("prefill_attention: D must be contiguous")
+    if rope_theta is not None and not rope_theta > 0:
+        raise ValueError("prefill_attention: rope_theta must be positive")
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    if not scale > 0:
+        raise ValueError("prefill_attention: scale must be positive")
+    n_st = (0, 0, 0)
+    if k_new is not None:
+        if k_new.dtype != BF16 or v_new.dtype != BF16 or \
+                tuple(k_new.shape) != (B, T, Hkv, D) or \
+                v_new.shape != k_new.shape or \
+                k_new.stride() != v_new.stride() or k_new.stride(3) != 1:
+            raise ValueError("prefill_attention: k_new/v_new must be bf16 "
+                             "[B,T,Hkv,D] with equal strides, D contiguous")
+        n_st = k_new.stride()[:3]
+    pos = positions.reshape(-1)
+    if pos.dtype != torch.int64 or not pos.is_cuda or \
+            pos.numel() not in (1, B):
+        raise ValueError("prefill_attention: positions must be a device "
+                         "int64 tensor with 1 or B elements")
+    pos = pos.contiguous()
+    pos_stride = 1 if (pos.numel() == B and B > 1) else 0
+    out = torch.empty(B, T, H, D, dtype=BF16, device=q.device)
+    try:
+        ext.prefill_attention(q.data_ptr(), _p(k_new), _p(v_new),
+                              k_cache.data_ptr(), v_cache.data_ptr(),
+                              pos.data_ptr(), pos_stride, out.data_ptr(),
+                              B, T, H, Hkv, S_max, D, scale,
+                              rope_theta is not None,
+                              float(rope_theta or 0.0), *q.stride()[:3],
+                              *n_st, *k_cache.stride()[:3], _stream())
+    except RuntimeError as e:      # alignment / stride / size refusals
+        if "prefill_attention:" not in str(e):
+            raise
+        raise ValueError(str(e)) from None
+    return out
+
+
 def sample_logits(logits: torch.Tensor, temperature: float, top_k: int = 0,
                   top_p: float = 1.0, seed: int = 0,
                   step: Optional[torch.Tensor] = None,

@@ -296,6 +296,29 @@ def decode_attention(q, k_cache, v_cache, positions, k_new=None, v_new=None,
                                scale, splits, rope_theta)
 
 
+def prefill_attention(q, k_cache, v_cache, positions, k_new=None, v_new=None,
+                      scale: Optional[float] = None,
+                      rope_theta: Optional[float] = None):
+    """Attention of a chunk of T query tokens over a KV cache (inference
+    only, no autograd): chunked prefill, a prompt behind a cached prefix, a
+    speculative verify step. q [B, T, H, D], k_new/v_new [B, T, Hkv, D],
+    caches [B, Hkv, S_max, D], D contiguous, any other strides; positions
+    int64 [1] or [B] on the tensors' device: the chunk's first position
+    p0[b], clamped into [0, S_max - T]. With (k_new, v_new) the chunk's rows
+    are first written in place into cache[b, :, p0 + t]; query t of batch
+    row b then attends cache rows 0 .. p0[b] + t of K/V head h // (H // Hkv).
+    With `rope_theta`, q and k_new are rotated (rotate-half, as ops.rope) at
+    p0 + t, each rounded once to the tensors' dtype, so the cache holds
+    rotated rows. Rows above p0 + T - 1 have no influence. Returns
+    [B, T, H, D], contiguous. On the GPU: bf16, D in {64, 128},
+    H / Hkv in {1, 2, 4, 8}; anything else raises ValueError."""
+    for t in (q, k_cache, v_cache, k_new, v_new):
+        assert t is None or not t.requires_grad, \
+            "prefill_attention has no backward"
+    return _backend(q).prefill_attention(q, k_cache, v_cache, positions,
+                                         k_new, v_new, scale, rope_theta)
+
+
 def _no_backward(name, *ts):
     # weights are Parameters: what must not happen is recording a graph
     assert not torch.is_grad_enabled() or \

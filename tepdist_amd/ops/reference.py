@@ -292,6 +292,53 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
         .to(q.dtype)
 
 
+def prefill_attention(q: torch.Tensor, k_cache: torch.Tensor,
+                      v_cache: torch.Tensor, positions: torch.Tensor,
+                      k_new: Optional[torch.Tensor] = None,
+                      v_new: Optional[torch.Tensor] = None,
+                      scale: Optional[float] = None,
+                      rope_theta: Optional[float] = None) -> torch.Tensor:
+    """A chunk of T query tokens over a KV cache. q: [B, T, H, D];
+    k_new/v_new: [B, T, Hkv, D]; caches [B, Hkv, S_max, D]; positions: int64
+    [1] or [B], the chunk's first position p0[b], clamped into
+    [0, S_max - T]. With (k_new, v_new) row t is first written IN PLACE into
+    cache[b, :, p0 + t]; query t then attends cache rows 0 .. p0[b] + t of
+    K/V head h // (H // Hkv). Rows above p0 + T - 1 have no influence
+    whatever they hold. With rope_theta, q and k_new are rotated at p0 + t
+    in fp32 and each rounded once to its dtype. fp32 math, returns
+    [B, T, H, D] in q.dtype."""
+    assert (k_new is None) == (v_new is None)
+    B, T, H, D = q.shape
+    Hkv, S_max = k_cache.shape[1], k_cache.shape[2]
+    assert H % Hkv == 0 and 1 <= T <= S_max, (H, Hkv, T, S_max)
+    G = H // Hkv
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    p0 = positions.reshape(-1).long().clamp(0, S_max - T)
+    assert p0.numel() in (1, B), positions.shape
+    rows = p0.expand(B)[:, None] + torch.arange(T, device=q.device)  # [B, T]
+    if rope_theta is not None:
+        q = rope_at(q, rows[:, :, None], rope_theta)
+    if k_new is not None:
+        assert k_new.shape == (B, T, Hkv, D) and v_new.shape == k_new.shape
+        if rope_theta is not None:
+            k_new = rope_at(k_new, rows[:, :, None], rope_theta)
+        bidx = torch.arange(B, device=q.device)[:, None]
+        k_cache[bidx, :, rows] = k_new.to(k_cache.dtype)
+        v_cache[bidx, :, rows] = v_new.to(v_cache.dtype)
+    dead = torch.arange(S_max, device=q.device) > rows[:, :, None]  # [B,T,S]
+    scores = torch.einsum("bthgd,bhsd->bhgts",
+                          q.float().reshape(B, T, Hkv, G, D),
+                          k_cache.float()) * scale
+    scores = scores.masked_fill(dead[:, None, None], float("-inf"))
+    p = torch.softmax(scores, dim=-1)
+    # rows no query sees contribute exact zeros, not 0 * NaN
+    unseen = dead[:, -1]                                          # [B, S]
+    v32 = v_cache.float().masked_fill(unseen[:, None, :, None], 0.0)
+    return torch.einsum("bhgts,bhsd->bthgd", p, v32).reshape(B, T, H, D) \
+        .to(q.dtype).contiguous()
+
+
 # --------------------------------------------------------------------------
 # Embedding
 # --------------------------------------------------------------------------
