@@ -17,7 +17,18 @@ interleaved. One JSON line per (site, M): median and min-max per contender,
 the needed weight bytes per skinny call time, and `wins`: whether the
 slowest skinny window beats the fastest window of both others.
 
-    bench_linear_decode.py [out.json]"""
+    bench_linear_decode.py [out.json]
+
+With --mx the contenders are the MX weight formats (ops.linear_decode_mx /
+ops.swiglu_linear_decode_mx on "mxfp8" and "mxfp4" weights) against the bf16
+skinny kernel and the library, on the same sites, windows and interleaving.
+Every contender gets its own number of weight copies by the same rule, sets
+* its weight bytes >= 512 MiB, so the smaller formats are not measured out
+of the Infinity Cache. `wins[fmt]`: the slowest window of the format beats
+the fastest bf16 skinny window. `max_abs_diff_vs_bf16_on_dq[fmt]`: against the
+bf16 skinny kernel on the dequantized weight (the same sum in another order).
+
+    bench_linear_decode.py --mx [out.json]"""
 import json
 import os
 import statistics
@@ -154,10 +165,85 @@ def run_site(model, site, N, K, form):
     return rows
 
 
-def main(out=None):
+def run_site_mx(model, site, N, K, form):
+    from tepdist_amd.ops import mx
+    torch.manual_seed(0)
+    nmat = 2 if form == "swiglu" else 1
+    w = torch.randn(N, K, dtype=BF16, device="cuda") * K ** -0.5
+    w2 = torch.randn(N, K, dtype=BF16, device="cuda") * K ** -0.5
+    q = {f: (ops.mx_quantize(w, f), ops.mx_quantize(w2, f))
+         for f in mx.FORMATS}
+    wbytes = {"bf16": nmat * N * K * 2}
+    wbytes.update({f: nmat * q[f][0].nbytes for f in mx.FORMATS})
+    sets = {f: max(4, -(-COLD_BYTES // nb)) for f, nb in wbytes.items()}
+
+    def copies(m, n):
+        return [mx.MXWeight(m.codes.clone(), m.scales.clone(), m.fmt, m.shape)
+                for _ in range(n)]
+
+    ws = [w.clone() for _ in range(sets["bf16"])]
+    ws2 = [w2.clone() for _ in range(sets["bf16"])] if nmat == 2 else None
+    qs = {f: (copies(q[f][0], sets[f]),
+              copies(q[f][1], sets[f]) if nmat == 2 else None)
+          for f in mx.FORMATS}
+    b = torch.randn(N, dtype=BF16, device="cuda")
+    rows = []
+    for M in MS:
+        x = torch.randn(M, K, dtype=BF16, device="cuda")
+        r = torch.randn(M, N, dtype=BF16, device="cuda")
+        bias = b if "bias" in form else None
+        res = r if "res" in form else None
+        act = "gelu" if form == "bias_gelu" else "none"
+        base = contenders(form, x, ws, ws2, b, r)
+        fns = {"skinny": (base["skinny"], sets["bf16"])}
+        for f in mx.FORMATS:
+            a, a2 = qs[f]
+            if nmat == 2:
+                fns[f] = (lambda i, a=a, a2=a2:
+                          ops.swiglu_linear_decode_mx(x, a[i], a2[i]), sets[f])
+            else:
+                fns[f] = (lambda i, a=a:
+                          ops.linear_decode_mx(x, a[i], bias, act, res),
+                          sets[f])
+        fns["lib"] = (base["lib"], sets["bf16"])
+        graphs, outs = {}, {}
+        for name, (fn, n) in fns.items():
+            graphs[name], outs[name] = capture(fn, n)
+        t = {k: [] for k in graphs}
+        for _ in range(WINDOWS):
+            for k, g in graphs.items():
+                t[k].append(window_us(g, fns[k][1]))
+        row = {"bench": "linear_decode_mx", "model": model, "site": site,
+               "form": form, "M": M, "N": N, "K": K, "sets": sets,
+               "weight_bytes": wbytes, "wins": {}, "max_abs_diff_vs_bf16_on_dq": {},
+               "weight_bytes_per_s": {}}
+        for k, v in t.items():
+            row[f"{k}_us"] = round(statistics.median(v), 2)
+            row[f"{k}_us_min_max"] = [round(min(v), 2), round(max(v), 2)]
+        for f in mx.FORMATS:
+            row["wins"][f] = max(t[f]) < min(t["skinny"])
+            row["weight_bytes_per_s"][f] = round(
+                wbytes[f] / (row[f"{f}_us"] * 1e-6))
+            with torch.no_grad():
+                dq = [ops.mx_dequantize(m) for m in q[f]]
+                want = ops.swiglu_linear_decode(x, dq[0], dq[1]) \
+                    if nmat == 2 else \
+                    ops.linear_decode(x, dq[0], bias, act, res)
+            row["max_abs_diff_vs_bf16_on_dq"][f] = round(
+                (outs[f].float() - want.float()).abs().max().item(), 4)
+        row["weight_bytes_per_s"]["bf16"] = round(
+            wbytes["bf16"] / (row["skinny_us"] * 1e-6))
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    return rows
+
+
+def main(*argv):
+    use_mx = "--mx" in argv
+    out = next((a for a in argv if not a.startswith("--")), None)
     rows = []
     for s in SITES:
-        rows += run_site(*s)
+        rows += run_site_mx(*s) if use_mx else run_site(*s)
         torch.cuda.empty_cache()
     if out:
         with open(out, "w") as f:

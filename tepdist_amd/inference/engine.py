@@ -49,7 +49,21 @@ query group; a site the kernel does not cover raises. "auto" = fused where
 the kernel covers the call and hip.prefill_auto has it measured ahead,
 composed elsewhere and on CPU (docs/KERNELS.md "Prefill attention over the
 cache"). generate(..., prefill_chunk=c) feeds the prompt in chunks of c
-tokens."""
+tokens.
+
+Weight format (weight_format=, or TEPDIST_WEIGHT_FORMAT): "bf16" (default)
+= the model's own weights, every path above as it was. "mxfp8" / "mxfp4" =
+weight-only OCP MX quantization (ops/mx.py): the constructor quantizes every
+block linear and the head once (Llama: qkv, o, gate, up, down, lm_head;
+GPT-2: qkv, proj, fc, out and wte as the head; embedding lookups, norms and
+biases stay bf16), and the model served is the quantized model at every
+site. A single-token site the MX plan covers runs ops.linear_decode_mx /
+ops.swiglu_linear_decode_mx with its fused epilogue, whatever decode_linear
+says: there is no "auto" rule, since going back to the bf16 weights would
+change the model. Every other site (T > 1, M > 64) runs ops.mx_dequantize
+into one scratch buffer sized for the largest weight, allocated once so a
+captured step can reuse it, then ops.linear (docs/KERNELS.md "Decode
+linears: MX weights")."""
 
 from __future__ import annotations
 
@@ -61,6 +75,7 @@ import torch
 
 from tepdist_amd import ops
 from tepdist_amd.models.llama import Llama
+from tepdist_amd.ops import mx
 from tepdist_amd.ops import reference as ref
 
 # query-group sizes H / Hkv the fused decode kernel covers
@@ -71,7 +86,8 @@ class Generator:
     def __init__(self, model, max_seq: Optional[int] = None,
                  decode_attn: Optional[str] = None,
                  decode_linear: Optional[str] = None,
-                 prefill_attn: Optional[str] = None):
+                 prefill_attn: Optional[str] = None,
+                 weight_format: Optional[str] = None):
         assert model.env.tp_size == 1, "generation engine: tp=1 layout"
         self.m = model
         self.cfg = model.cfg
@@ -100,6 +116,49 @@ class Generator:
                 f"prefill_attn must be 'composed', 'fused' or 'auto', "
                 f"got {prefill_attn!r}")
         self.prefill_attn = prefill_attn
+        if weight_format is None:
+            weight_format = os.environ.get("TEPDIST_WEIGHT_FORMAT", "bf16")
+        if weight_format not in ("bf16",) + mx.FORMATS:
+            raise ValueError(
+                f"weight_format must be 'bf16', 'mxfp8' or 'mxfp4', "
+                f"got {weight_format!r}")
+        self.weight_format = weight_format
+        # id(parameter) -> its MXWeight; empty = serve the bf16 weights
+        self.mxw = {}
+        if weight_format != "bf16":
+            ws = self.quantized_params(model)
+            self.mxw = {id(w): mx.mx_quantize(w, weight_format) for w in ws}
+            self._dq = torch.empty(max(w.numel() for w in ws),
+                                   dtype=torch.bfloat16, device=ws[0].device)
+
+    @staticmethod
+    def quantized_params(model):
+        """The weights a weight_format other than "bf16" quantizes: every
+        block linear and the head."""
+        if isinstance(model, Llama):
+            names, head = ("w_qkv", "w_o", "w_gate", "w_up", "w_down"), \
+                model.lm_head
+        else:
+            names, head = ("w_qkv", "w_proj", "w_fc", "w_out"), model.wte
+        return [getattr(b, n) for b in model.blocks for n in names] + [head]
+
+    def _mx_site(self, x2, mw, bias=None, act="none", residual=None,
+                 mw_up=None) -> bool:
+        """Whether a single-token site on x2 [M, K] runs the MX decode ops:
+        on CUDA where the MX plan covers it, on CPU (the reference op)
+        always."""
+        if not x2.is_cuda:
+            return True
+        from tepdist_amd.ops import hip
+        return not hip.skinny_mx_why_not(
+            x2, mw, hip.skinny_epi(bias, act, residual), mw_up, residual)
+
+    def _dequantized(self, mw, dtype):
+        """bf16 weight of mw in the shared scratch buffer: valid until the
+        next call."""
+        N, K = mw.shape
+        w = ops.mx_dequantize(mw, out=self._dq[:N * K].view(N, K))
+        return w if dtype == w.dtype else w.to(dtype)
 
     def _fused_decode(self, x, D, G: int = 1) -> bool:
         """Whether single-token steps on tensors like x run the fused
@@ -156,7 +215,17 @@ class Generator:
         """residual + act(x @ w^T + bias) in residual's shape (x's leading
         dims without one). decode: a single-token site, which may run
         ops.linear_decode with everything in its epilogue."""
-        if decode:
+        mw = self.mxw.get(id(w))
+        if mw is not None:
+            x2 = x.reshape(-1, x.shape[-1])
+            r2 = None if residual is None else \
+                residual.reshape(-1, w.shape[0])
+            if decode and self._mx_site(x2, mw, bias, act, r2):
+                y = ops.linear_decode_mx(x2, mw, bias, act, r2)
+                return y.reshape(*x.shape[:-1], w.shape[0]) \
+                    if residual is None else y.reshape(residual.shape)
+            w = self._dequantized(mw, x.dtype)
+        elif decode:
             x2 = x.reshape(-1, x.shape[-1])
             r2 = None if residual is None else \
                 residual.reshape(-1, w.shape[0])
@@ -260,7 +329,13 @@ class Generator:
         cfg = self.cfg
         B, T, d = x.shape
         hn = ops.rmsnorm(x.reshape(B * T, d), blk.ln2_g, cfg.rms_eps)
-        if T == 1 and self._skinny_site(hn, blk.w_gate, w_up=blk.w_up):
+        mg, mu = self.mxw.get(id(blk.w_gate)), self.mxw.get(id(blk.w_up))
+        if mg is not None and T == 1 and self._mx_site(hn, mg, mw_up=mu):
+            h = ops.swiglu_linear_decode_mx(hn, mg, mu)
+        elif mg is not None:    # one scratch buffer: gate, then up
+            g = ops.linear(hn, self._dequantized(mg, hn.dtype))
+            h = ops.swiglu(g, ops.linear(hn, self._dequantized(mu, hn.dtype)))
+        elif T == 1 and self._skinny_site(hn, blk.w_gate, w_up=blk.w_up):
             h = ops.swiglu_linear_decode(hn, blk.w_gate, blk.w_up)
         else:
             h = ops.swiglu(ops.linear(hn, blk.w_gate),

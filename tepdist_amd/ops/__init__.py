@@ -12,6 +12,9 @@ from tepdist_amd.ops.interface import (  # noqa: F401
     prefill_attention,
     linear_decode,
     swiglu_linear_decode,
+    linear_decode_mx,
+    swiglu_linear_decode_mx,
+    mx_dequantize,
     sample_logits,
     MoERoute,
     moe_route,
@@ -25,6 +28,8 @@ from tepdist_amd.ops.interface import (  # noqa: F401
     rope,
     swiglu,
 )
+
+from tepdist_amd.ops.mx import MXWeight, mx_quantize  # noqa: E402,F401
 
 # torch.fx: leaf-wrap the public ops IN THIS NAMESPACE (clients call
 # ops.<name>), so generic capture (ir/capture.from_fx) records op nodes

@@ -29,6 +29,7 @@ SOURCES = [
     "decode_attention.hip",
     "prefill_attention.hip",
     "skinny_gemm.hip",
+    "skinny_mx_gemm.hip",
     "sampling.hip",
     "moe_route.hip",
     "transpose.hip",
@@ -54,10 +55,12 @@ SOURCES = [
 # -Xclang reaches the host pass too, which has no such feature and ignores
 # it (hipcc's -Xarch_device does not take options with arguments).
 # prefill_attention.hip takes the same flag: its softmax rescale and
-# epilogue would otherwise pair into v_pk_mul_f32.
+# epilogue would otherwise pair into v_pk_mul_f32. skinny_mx_gemm.hip shares
+# skinny_gemm.hip's LDS sum and epilogue, and its reason.
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
     "skinny_gemm.hip": _NO_PK_F32,
+    "skinny_mx_gemm.hip": _NO_PK_F32,
     "prefill_attention.hip": _NO_PK_F32,
 }
 
@@ -79,6 +82,7 @@ def _needs_build() -> bool:
                                           CSRC / "lds_frag.h",
                                           CSRC / "gemm_plan.h",
                                           CSRC / "skinny_plan.h",
+                                          CSRC / "skinny_mx_plan.h",
                                           CSRC / "gemm_tile.h",
                                           CSRC / "rope_common.h",
                                           Path(__file__)]

@@ -13,6 +13,7 @@
 #include "common.h"
 #include "gemm_plan.h"
 #include "kernels.h"
+#include "skinny_mx_plan.h"
 #include "skinny_plan.h"
 
 namespace py = pybind11;
@@ -92,6 +93,45 @@ PYBIND11_MODULE(_tepdist_hip, m) {
                           p.why_not ? p.why_not : "");
   }, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("ldx"),
      py::arg("ldw"), py::arg("epi") = 0, py::arg("dual") = false);
+
+  m.def("skinny_mx_gemm", [](uintptr_t x, uintptr_t codes, uintptr_t scales,
+                             uintptr_t codes2, uintptr_t scales2,
+                             uintptr_t bias, uintptr_t res, uintptr_t y,
+                             int M, int N, int K, int bits, int64_t ldx,
+                             int64_t ldc, int64_t lds, int64_t ldc2,
+                             int64_t lds2, int64_t ldr, int64_t ldy, int epi,
+                             uintptr_t stream) {
+    skinny_mx_gemm(reinterpret_cast<void*>(x), reinterpret_cast<void*>(codes),
+                   reinterpret_cast<void*>(scales),
+                   reinterpret_cast<void*>(codes2),
+                   reinterpret_cast<void*>(scales2),
+                   reinterpret_cast<void*>(bias),
+                   reinterpret_cast<void*>(res), reinterpret_cast<void*>(y),
+                   M, N, K, bits, ldx, ldc, lds, ldc2, lds2, ldr, ldy, epi,
+                   S(stream));
+    check_launch();
+  });
+
+  // (mt, rows, waves, k_per_wave, unroll, why_not) — host-only, no GPU
+  m.def("skinny_mx_plan", [](int M, int N, int K, int bits, int64_t ld_codes,
+                             int64_t ld_scales, int epi, bool dual) {
+    const SkinnyMxPlan p =
+        skinny_mx_plan(M, N, K, bits, ld_codes, ld_scales, epi, dual);
+    return py::make_tuple(p.mt, p.rows, p.waves, p.k_per_wave, p.unroll,
+                          p.why_not ? p.why_not : "");
+  }, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("bits"),
+     py::arg("ld_codes"), py::arg("ld_scales"), py::arg("epi") = 0,
+     py::arg("dual") = false);
+
+  m.def("mx_dequantize", [](uintptr_t codes, uintptr_t scales, uintptr_t out,
+                            int N, int K, int bits, int64_t ldc, int64_t lds,
+                            int64_t ldo, uintptr_t stream) {
+    mx_dequantize_bf16(reinterpret_cast<void*>(codes),
+                       reinterpret_cast<void*>(scales),
+                       reinterpret_cast<void*>(out), N, K, bits, ldc, lds,
+                       ldo, S(stream));
+    check_launch();
+  });
 
   m.def("transpose", [](uintptr_t in, uintptr_t out, int R, int C,
                         int64_t si, int64_t so, int batch,

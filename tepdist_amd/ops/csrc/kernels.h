@@ -63,6 +63,25 @@ void skinny_gemm_bf16(const void* x, const void* w, const void* w2,
                       int N, int K, int64_t ldx, int64_t ldw, int64_t ldw2,
                       int64_t ldr, int64_t ldy, int epi, hipStream_t stream);
 
+// --- Skinny-M decode linear on MX weights (skinny_mx_gemm.hip) ---------------
+// y[M, N] = epi(x[M, K] @ dq(W)[N, K]^T) for 1 <= M <= 64, K % 128 == 0. W is
+// OCP MX: codes (bits = 4: e2m1, two per byte, even k low; bits = 8: e4m3)
+// with row stride ldc bytes, and one e8m0 scale byte per 32 k with row
+// stride lds bytes. codes2 / scales2 non-null: the dual SwiGLU form, epi 0
+// only. x, bias, res, y and epi as skinny_gemm_bf16. Throws with
+// skinny_mx_plan()'s reason when the call is not covered.
+void skinny_mx_gemm(const void* x, const void* codes, const void* scales,
+                    const void* codes2, const void* scales2, const void* bias,
+                    const void* res, void* y, int M, int N, int K, int bits,
+                    int64_t ldx, int64_t ldc, int64_t lds, int64_t ldc2,
+                    int64_t lds2, int64_t ldr, int64_t ldy, int epi,
+                    hipStream_t stream);
+// out[N, K] (bf16, row stride ldo elements) = dq(W), K % 32 == 0, with the
+// same conversion instructions as the GEMM.
+void mx_dequantize_bf16(const void* codes, const void* scales, void* out,
+                        int N, int K, int bits, int64_t ldc, int64_t lds,
+                        int64_t ldo, hipStream_t stream);
+
 // --- Transpose -------------------------------------------------------------
 // out[c][r] = in[r][c] per batch (strides in elements).
 void transpose_bf16(const void* in, void* out, int R, int C,

@@ -242,6 +242,108 @@ def swiglu_linear_decode(x, w_gate, w_up):
     return _skinny(x, w_gate, w_up, None, None, 0)
 
 
+# Decode-step linears on MX weights (csrc/skinny_mx_gemm.hip): the same
+# contract as above with W an ops.mx.MXWeight, read in its interchange
+# layout. Coverage comes from csrc/skinny_mx_plan.h (ext.skinny_mx_plan).
+
+def skinny_mx_why_not(x: torch.Tensor, mw, epi: int = 0, mw_up=None,
+                      residual: Optional[torch.Tensor] = None) -> str:
+    """'' when skinny_mx_gemm takes this call, else why not."""
+    from tepdist_amd.ops import mx
+    ts = [t for t in (x, residual) if t is not None]
+    if any(t.dtype != BF16 or t.dim() != 2 or t.stride(1) != 1 for t in ts):
+        return "x and residual must be 2-D bf16 with a contiguous last dim"
+    M, K = x.shape
+    N = mw.shape[0]
+    if mw.shape[1] != K or (mw_up is not None and (
+            mw_up.shape != mw.shape or mw_up.fmt != mw.fmt)):
+        return "weight shapes or formats do not match x"
+    if residual is not None and tuple(residual.shape) != (M, N):
+        return "residual must be [M, N]"
+    for w in (mw, mw_up):
+        if w is None:
+            continue
+        mx.check(w)
+        if w.codes.stride(1) != 1 or w.scales.stride(1) != 1 or \
+                not w.codes.is_cuda or not w.scales.is_cuda:
+            return "codes and scales must be device tensors with a " \
+                   "contiguous last dim"
+        why = ext.skinny_mx_plan(M, N, K, mx.bits(w.fmt), w.codes.stride(0),
+                                 w.scales.stride(0), epi,
+                                 mw_up is not None)[5]
+        if why:
+            return why
+        if w.codes.data_ptr() % 16 or w.scales.data_ptr() % 4:
+            return "codes need a 16-byte-aligned base, scales a " \
+                   "4-byte-aligned one"
+    if x.data_ptr() % 16 or x.stride(0) % 8:
+        return "x needs a 16-byte-aligned base and rows"
+    return ""
+
+
+def _skinny_mx(name, x, mw, mw_up, bias, residual, epi):
+    from tepdist_amd.ops import mx
+    why = skinny_mx_why_not(x, mw, epi, mw_up, residual)
+    if why:
+        raise ValueError(f"{name}: not covered by the MX skinny kernel: "
+                         f"{why}")
+    M, K = x.shape
+    N = mw.shape[0]
+    if bias is not None:
+        assert bias.dtype == BF16 and bias.shape == (N,)
+        bias = bias.contiguous()
+    y = torch.empty(M, N, dtype=BF16, device=x.device)
+    up = mw_up is not None
+    ext.skinny_mx_gemm(x.data_ptr(), mw.codes.data_ptr(),
+                       mw.scales.data_ptr(),
+                       mw_up.codes.data_ptr() if up else 0,
+                       mw_up.scales.data_ptr() if up else 0, _p(bias),
+                       _p(residual), y.data_ptr(), M, N, K, mx.bits(mw.fmt),
+                       x.stride(0), mw.codes.stride(0), mw.scales.stride(0),
+                       mw_up.codes.stride(0) if up else 0,
+                       mw_up.scales.stride(0) if up else 0,
+                       residual.stride(0) if residual is not None else 0, N,
+                       epi, _stream())
+    return y
+
+
+def linear_decode_mx(x, mw, bias=None, act: str = "none", residual=None):
+    return _skinny_mx("linear_decode_mx", x, mw, None, bias, residual,
+                      skinny_epi(bias, act, residual))
+
+
+def swiglu_linear_decode_mx(x, mw_gate, mw_up):
+    return _skinny_mx("swiglu_linear_decode_mx", x, mw_gate, mw_up, None,
+                      None, 0)
+
+
+def mx_dequantize(mw, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bf16 [N, K] of an MXWeight, with the GEMM's conversion instructions.
+    out: a bf16 [N, K] tensor with a contiguous last dim to write into."""
+    from tepdist_amd.ops import mx
+    N, K = mx.check(mw)
+    codes, scales = mw.codes, mw.scales
+    if out is None:
+        out = torch.empty(N, K, dtype=BF16, device=codes.device)
+    if out.dtype != BF16 or tuple(out.shape) != (N, K) or \
+            out.stride(1) != 1 or out.device != codes.device:
+        raise ValueError(f"mx_dequantize: out must be bf16 {(N, K)} with a "
+                         "contiguous last dim on the codes' device")
+    if not codes.is_cuda or codes.stride(1) != 1 or scales.stride(1) != 1:
+        raise ValueError("mx_dequantize: codes and scales must be device "
+                         "tensors with a contiguous last dim")
+    try:
+        ext.mx_dequantize(codes.data_ptr(), scales.data_ptr(),
+                          out.data_ptr(), N, K, mx.bits(mw.fmt),
+                          codes.stride(0), scales.stride(0), out.stride(0),
+                          _stream())
+    except RuntimeError as e:      # alignment / stride refusals
+        if "mx_dequantize:" not in str(e):
+            raise
+        raise ValueError(str(e)) from None
+    return out
+
+
 def _bias_sum(t: torch.Tensor) -> torch.Tensor:
     """Column sums of contiguous t [rows, cols] as bf16 [cols] (the bias
     gradient), accumulated in a zeroed fp32 workspace."""

@@ -348,6 +348,35 @@ def swiglu_linear_decode(x, w_gate, w_up):
     return _backend(x).swiglu_linear_decode(x, w_gate, w_up)
 
 
+def linear_decode_mx(x, mw, bias=None, act: str = "none", residual=None):
+    """linear_decode against a weight-only quantized W: mw is an
+    ops.mx.MXWeight ("mxfp8" or "mxfp4", from ops.mx_quantize) of shape
+    [N, K]. The result is defined as linear_decode on the dequantized weight
+    (an MX element times its power-of-two scale is exact in bf16): fp32
+    accumulation, one rounding. On the GPU this is the dequantizing skinny
+    kernel, which reads codes and scales in their interchange layout: K a
+    multiple of 128, code rows 16-byte and scale rows 4-byte aligned; a call
+    it does not cover raises with the reason. Inference only."""
+    _no_backward("linear_decode_mx", x, bias, residual)
+    return _backend(x).linear_decode_mx(x, mw, bias, act, residual)
+
+
+def swiglu_linear_decode_mx(x, mw_gate, mw_up):
+    """silu(x @ dq(mw_gate)^T) * (x @ dq(mw_up)^T) in one pass over both
+    quantized weights (inference only). Coverage as linear_decode_mx; both
+    weights in one format."""
+    _no_backward("swiglu_linear_decode_mx", x)
+    return _backend(x).swiglu_linear_decode_mx(x, mw_gate, mw_up)
+
+
+def mx_dequantize(mw, out=None):
+    """bf16 [N, K] of an MXWeight: every code's value times its block's
+    scale, exactly. out: a bf16 [N, K] tensor to write into. On the GPU a
+    HIP kernel with the conversion instructions of linear_decode_mx (K a
+    multiple of 32, 16-byte-aligned code rows)."""
+    return _backend(mw.codes).mx_dequantize(mw, out)
+
+
 def sample_logits(logits, *, temperature: float, top_k: int = 0,
                   top_p: float = 1.0, seed: int = 0, step=None, u=None,
                   vocab: Optional[int] = None, out=None,

@@ -92,6 +92,25 @@ def swiglu_linear_decode(x: torch.Tensor, w_gate: torch.Tensor,
     return (g * torch.sigmoid(g) * (xf @ w_up.float().t())).to(x.dtype)
 
 
+def mx_dequantize(mw, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bf16 [N, K] of an ops.mx.MXWeight (mx.dequantize_ref)."""
+    from tepdist_amd.ops import mx
+    w = mx.dequantize_ref(mw)
+    return w if out is None else out.copy_(w)
+
+
+def linear_decode_mx(x: torch.Tensor, mw, bias=None, act: str = "none",
+                     residual=None) -> torch.Tensor:
+    """linear_decode on the dequantized weight."""
+    return linear_decode(x, mx_dequantize(mw), bias, act, residual)
+
+
+def swiglu_linear_decode_mx(x: torch.Tensor, mw_gate, mw_up) -> torch.Tensor:
+    """swiglu_linear_decode on the dequantized weights."""
+    return swiglu_linear_decode(x, mx_dequantize(mw_gate),
+                                mx_dequantize(mw_up))
+
+
 # --------------------------------------------------------------------------
 # GELU (tanh approximation, as GPT-2 uses)
 # --------------------------------------------------------------------------
