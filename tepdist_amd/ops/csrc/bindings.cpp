@@ -72,6 +72,21 @@ PYBIND11_MODULE(_tepdist_hip, m) {
      py::arg("ldb"), py::arg("a_kc") = true, py::arg("b_kc") = true,
      py::arg("epi") = 0, py::arg("batch") = 1);
 
+  // "" when one operand's base address and batch stride suit the loads its
+  // ld selects under that call's plan, else the reason ext.gemm refuses it
+  // with — host-only, needs no GPU
+  m.def("gemm_operand_why_not", [](int M, int N, int K, int lda, int ldb,
+                                   bool a_kc, bool b_kc, int epi, int batch,
+                                   bool is_a, uintptr_t base,
+                                   int64_t stride) {
+    const GemmPlan p = gemm_plan(M, N, K, lda, ldb, a_kc, b_kc, epi, batch);
+    const char* why = operand_why_not(p, base, is_a ? lda : ldb,
+                                      is_a ? a_kc : b_kc, stride, batch);
+    return std::string(why ? why : "");
+  }, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("lda"),
+     py::arg("ldb"), py::arg("a_kc"), py::arg("b_kc"), py::arg("epi"),
+     py::arg("batch"), py::arg("is_a"), py::arg("base"), py::arg("stride"));
+
   m.def("skinny_gemm", [](uintptr_t x, uintptr_t w, uintptr_t w2,
                           uintptr_t bias, uintptr_t res, uintptr_t y, int M,
                           int N, int K, int64_t ldx, int64_t ldw,

@@ -412,6 +412,12 @@ void gemm_bf16(const void* A, const void* B, void* C, void* c_pre,
   const GemmPlan p = gemm_plan(M, N, K, lda, ldb, a_kc, b_kc, epi, batch);
   if (p.kernel == 0)
     throw std::runtime_error(std::string("gemm_bf16: ") + p.why_not);
+  if (const char* why = operand_why_not(p, reinterpret_cast<uintptr_t>(A),
+                                        lda, a_kc, stride_a, batch))
+    throw std::runtime_error(std::string("gemm_bf16: A: ") + why);
+  if (const char* why = operand_why_not(p, reinterpret_cast<uintptr_t>(B),
+                                        ldb, b_kc, stride_b, batch))
+    throw std::runtime_error(std::string("gemm_bf16: B: ") + why);
   const bool colsum = colsum_out != nullptr;
   if (colsum) {
     if (const char* why = colsum_why_not(p, a_kc, b_kc, batch))

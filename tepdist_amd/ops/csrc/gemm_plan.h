@@ -121,6 +121,31 @@ inline GemmPlan gemm_plan(int M, int N, int K, int lda, int ldb, bool a_kc,
   return {T128, split_k, k_chunk, nullptr};
 }
 
+// The plan above and the kernels judge an operand's alignment from its
+// leading dimension alone (ld % 8 == 0: 16-byte vector loads and the
+// global_load_lds DMA; a k-outer operand of the 128 kernel with ld even:
+// 4-byte loads). Those loads also need the operand's first element, and
+// every batch element's, on the same boundary, which a column slice at an
+// odd offset of a wide tensor does not give. nullptr when the base address
+// and batch stride (in elements) of one bf16 operand of plan `p` suit the
+// loads its ld selects, else why not. gemm_bf16 refuses such a call before
+// it launches; callers copy the operand instead (ops/hip.py).
+inline const char* operand_why_not(const GemmPlan& p, uintptr_t base, int ld,
+                                   bool kc, int64_t stride, int batch) {
+  int bytes = 2;  // element loads
+  if ((ld & 7) == 0 && (kc || p.kernel == plan::T256)) bytes = 16;
+  else if (!kc && (ld & 1) == 0) bytes = 4;
+  if (base % bytes != 0)
+    return bytes == 16
+               ? "operand rows are 16-byte multiples (ld % 8 == 0) but its "
+                 "base address is not 16-byte aligned"
+               : "k-outer operand rows are 4-byte multiples (ld even) but "
+                 "its base address is not 4-byte aligned";
+  if (batch > 1 && (stride * 2) % bytes != 0)
+    return "operand batch stride breaks the alignment its ld promises";
+  return nullptr;
+}
+
 // Column sums of A (colsum[m] = sum over k of A[k][m], wgrad's bias
 // gradient) come only from the 256 kernel on two k-outer operands: nullptr
 // when plan `p` of a call with these layouts can produce them, else why not.

@@ -95,6 +95,28 @@ def assert_within_ulp(got: torch.Tensor, ref64: torch.Tensor, floor=0.0,
 
 
 # --------------------------------------------------------------------------
+# GEMM (the hand kernels of csrc/gemm.hip and csrc/gemm256.hip)
+# --------------------------------------------------------------------------
+
+def gemm(a, b, a_kc: bool, b_kc: bool, bias=None):
+    """C = A B^T (+ bias per column) of operands as the kernels store them:
+    a is [..., M, K] when a_kc (k contiguous) else [..., K, M], b is
+    [..., N, K] when b_kc else [..., K, N]; leading batch dims broadcast.
+    Returns (ref64, abs_product): the float64 product and |A| |B|^T + |bias|,
+    the sum of the magnitudes of the terms that form each element, which is
+    what a summation error bound scales with."""
+    a, b = f64(a), f64(b)
+    if not a_kc:
+        a = a.transpose(-1, -2)
+    if b_kc:
+        b = b.transpose(-1, -2)
+    ref, mag = a @ b, a.abs() @ b.abs()
+    if bias is not None:
+        ref, mag = ref + f64(bias), mag + f64(bias).abs()
+    return ref, mag
+
+
+# --------------------------------------------------------------------------
 # LayerNorm / add + LayerNorm / RMSNorm
 # --------------------------------------------------------------------------
 

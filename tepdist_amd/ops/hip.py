@@ -95,6 +95,17 @@ def _pick_backend(key, hip_fn, blt_fn):
     return hip_fn if th <= tb else blt_fn
 
 
+def _base_suits_ld(t: torch.Tensor, ld: int, batch_stride: int = 0) -> bool:
+    """The hand GEMM picks an operand's loads from its leading dimension:
+    16-byte vectors and DMA when ld % 8 == 0, 4-byte pairs when ld is even.
+    They need the first element (and each batch element's) on that boundary
+    too, which a column slice at an odd offset of a wider tensor lacks.
+    ext.gemm refuses such an operand (csrc/gemm_plan.h operand_why_not);
+    callers that accept arbitrary views copy it first."""
+    need = 16 if ld % 8 == 0 else (4 if ld % 2 == 0 else 2)
+    return t.data_ptr() % need == 0 and (batch_stride * 2) % need == 0
+
+
 def _gemm_raw(a: torch.Tensor, b_stored: torch.Tensor, a_kc: bool, b_kc: bool,
               M: int, N: int, K: int, lda: int, ldb: int,
               sa: int, sb: int, batch: int, bias=None, epi: int = 0,
@@ -128,6 +139,13 @@ def linear_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor],
     x = x.contiguous()
     M, K = x.shape
     N = w.shape[0]
+    if not _base_suits_ld(x, K):
+        x = x.clone(memory_format=torch.contiguous_format)
+    # w may be a row slice of a wider tensor (ld = w.stride(0)); anything
+    # else that is not k-contiguous, or starts off its rows' alignment, is
+    # copied
+    if w.stride(1) != 1 or not _base_suits_ld(w, w.stride(0)):
+        w = w.clone(memory_format=torch.contiguous_format)
     if act == "none":
         epi = 1 if bias is not None else 0
     elif act == "gelu":
@@ -651,7 +669,7 @@ def _matmul_hip(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     Shapes: [M,K]@[K,N] or batched [B,M,K]@[B,K,N] (B may broadcast)."""
     assert a.dtype == BF16 and b.dtype == BF16
     squeeze = a.dim() == 2 and b.dim() == 2
-    lead_shape = (a if a.dim() >= b.dim() else b).shape[:-2]
+    lead_shape = torch.broadcast_shapes(a.shape[:-2], b.shape[:-2])
     if a.dim() == 2:
         a = a.unsqueeze(0)
     if b.dim() == 2:
@@ -668,21 +686,25 @@ def _matmul_hip(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     K2, N = b.shape[-2], b.shape[-1]
     assert K == K2, (a.shape, b.shape)
     batch = max(a.shape[0], b.shape[0])
+    # a flattened batch broadcasts as a whole (stride 0) or not at all
+    if a.shape[0] not in (1, batch) or b.shape[0] not in (1, batch) \
+            or batch != math.prod(lead_shape):
+        raise ValueError("matmul: batch dims must match or be 1 as a whole, "
+                         f"got {tuple(a.shape)} @ {tuple(b.shape)}")
 
     def layout(t, contraction_is_last: bool):
         # returns (kc, ld, batch_stride)
-        if t.stride(-1) == 1:
-            inner_last = True
-            ld = t.stride(-2)
-        elif t.stride(-2) == 1:
-            inner_last = False
-            ld = t.stride(-1)
-        else:
+        if t.stride(-1) != 1 and t.stride(-2) != 1:
             t = t.contiguous()
-            inner_last = True
-            ld = t.stride(-2)
-        kc = (inner_last == contraction_is_last)
+        inner_last = t.stride(-1) == 1
+        ld = t.stride(-2) if inner_last else t.stride(-1)
         bs = t.stride(0) if t.shape[0] > 1 else 0
+        if not _base_suits_ld(t, ld, bs):
+            # a view that starts off the alignment its ld promises
+            t = t.clone(memory_format=torch.contiguous_format)
+            inner_last, ld = True, t.stride(-2)
+            bs = t.stride(0) if t.shape[0] > 1 else 0
+        kc = (inner_last == contraction_is_last)
         return t, kc, ld, bs
 
     a, a_kc, lda, sa = layout(a, contraction_is_last=True)

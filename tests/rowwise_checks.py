@@ -369,15 +369,19 @@ def activation_inputs(n, seed):
     return x
 
 
+def gelu_floor(x64):
+    # y = 0.5 x (1 + t): t = tanh(z) has absolute error dt ~ 2^-21 (the
+    # reciprocal's ulp at 2 / (e + 1) <= 2, exp2's ulp, the subtraction),
+    # so y errs by 0.5 |x| dt; 2^-20 * max(1, |x|) is twice that
+    return ELEM * x64.abs().clamp_min(1.0)
+
+
 def check_gelu(be, dev, n, cap=None):
     x = activation_inputs(n, n)
     dy = randn(gen(n + 1), n)
     x64, dy64 = o.f64(x), o.f64(dy)
     big = x64.abs().clamp_min(1.0)
-    # y = 0.5 x (1 + t): t = tanh(z) has absolute error dt ~ 2^-21 (the
-    # reciprocal's ulp at 2 / (e + 1) <= 2, exp2's ulp, the subtraction),
-    # so y errs by 0.5 |x| dt; 2^-20 * max(1, |x|) is twice that
-    judge(be.gelu_fwd(x.to(dev)), o.gelu_fwd(x), ELEM * big,
+    judge(be.gelu_fwd(x.to(dev)), o.gelu_fwd(x), gelu_floor(x64),
           f"gelu_fwd[{n}]", cap)
     # dgelu = 0.5 (1 + t) + 0.5 x (1 - t^2) z'(x): the forward's floor
     # times |dy|
