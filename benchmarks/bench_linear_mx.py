@@ -1,0 +1,140 @@
+"""Tiled MX linear microbenchmark: ops.linear_mx (csrc/mx_gemm.hip) against
+the dequantize-then-GEMM path the engine runs without it, at the flagship
+sites and M = 128 .. 4096, by the method of bench_linear_decode.py --mx
+(whose capture / window helpers it uses).
+
+Contenders per (site, M, format):
+  "dequant"  ops.mx_dequantize into one scratch buffer + ops.linear, plus
+             the residual add / swiglu launches the engine issues: the
+             yardstick (mx_linear="dequant");
+  "fused"    ops.linear_mx with the tile the plan picks (for the SwiGLU site
+             two calls + ops.swiglu, as the engine does);
+  "other"    the same with the other tile, at M <= 512 only, so that the
+             plan's tile rule is measured;
+  "floor"    ops.linear on a weight dequantized beforehand: what "dequant"
+             cannot go below. For information.
+Each contender is a hipGraph of `sets` back-to-back calls, call i on its own
+copy of the weight, sets * its weight bytes >= 512 MiB; median (min-max) of
+WINDOWS interleaved windows of REPLAYS replays. `wins`: the slowest "fused"
+window beats the fastest "dequant" window.
+
+    bench_linear_mx.py [out.json] [--sites qkv,o] [--ms 128,512]"""
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import torch
+
+from bench_linear_decode import BF16, COLD_BYTES, SITES, WINDOWS, capture, \
+    window_us
+from tepdist_amd import ops
+from tepdist_amd.ops import hip, mx
+
+MS = (128, 256, 512, 1024, 2048, 4096)
+
+
+def run_site(model, site, N, K, form, ms):
+    torch.manual_seed(0)
+    nmat = 2 if form == "swiglu" else 1
+    w = [torch.randn(N, K, dtype=BF16, device="cuda") * K ** -0.5
+         for _ in range(nmat)]
+    b = torch.randn(N, dtype=BF16, device="cuda")
+    scratch = torch.empty(N, K, dtype=BF16, device="cuda")
+    rows = []
+    for fmt in mx.FORMATS:
+        q = [ops.mx_quantize(t, fmt) for t in w]
+        dq = [ops.mx_dequantize(m) for m in q]
+        nbytes = {"mx": nmat * q[0].nbytes, "bf16": nmat * N * K * 2}
+        sets = {k: max(4, -(-COLD_BYTES // v)) for k, v in nbytes.items()}
+        qs = [[mx.MXWeight(m.codes.clone(), m.scales.clone(), m.fmt, m.shape)
+               for _ in range(sets["mx"])] for m in q]
+        ds = [[t.clone() for _ in range(sets["bf16"])] for t in dq]
+        for M in ms:
+            x = torch.randn(M, K, dtype=BF16, device="cuda")
+            r = torch.randn(M, N, dtype=BF16, device="cuda")
+            bias = b if "bias" in form else None
+            res = r if "res" in form else None
+            act = "gelu" if form == "bias_gelu" else "none"
+            epi = hip.skinny_epi(bias, act, res)
+
+            def tail(ys):
+                if nmat == 2:
+                    return ops.swiglu(ys[0], ys[1])
+                return ys[0] if res is None else res + ys[0]
+
+            def dequant(i):
+                return tail([ops.linear(x, ops.mx_dequantize(a[i],
+                                                             out=scratch),
+                                        bias, act) for a in qs])
+
+            def floor(i):
+                return tail([ops.linear(x, a[i], bias, act) for a in ds])
+
+            def fused(tile):
+                if nmat == 2:
+                    return lambda i: ops.swiglu(*(hip._mx_gemm_raw(
+                        x, a[i], None, None, 0, tile) for a in qs))
+                return lambda i: hip._mx_gemm_raw(x, qs[0][i], bias, res,
+                                                  epi, tile)
+
+            tile = hip.ext.mx_gemm_plan(
+                M, N, K, mx.bits(fmt), q[0].codes.stride(0),
+                q[0].scales.stride(0))[0]
+            fns = {"dequant": (dequant, sets["mx"]),
+                   "fused": (fused(tile), sets["mx"]),
+                   "floor": (floor, sets["bf16"])}
+            if M <= 512:
+                fns["other"] = (fused(64 if tile == 128 else 128), sets["mx"])
+            graphs, outs = {}, {}
+            for name, (fn, n) in fns.items():
+                graphs[name], outs[name] = capture(fn, n)
+            t = {k: [] for k in graphs}
+            for _ in range(WINDOWS):
+                for k, g in graphs.items():
+                    t[k].append(window_us(g, fns[k][1]))
+            row = {"bench": "linear_mx", "model": model, "site": site,
+                   "form": form, "fmt": fmt, "M": M, "N": N, "K": K,
+                   "tile": tile, "sets": sets, "weight_bytes": nbytes}
+            for k, v in t.items():
+                row[f"{k}_us"] = round(statistics.median(v), 2)
+                row[f"{k}_us_min_max"] = [round(min(v), 2), round(max(v), 2)]
+            row["wins"] = max(t["fused"]) < min(t["dequant"])
+            if "other" in t:
+                row["other_tile_wins"] = max(t["other"]) < min(t["fused"])
+            row["fused_tflops"] = round(
+                nmat * 2.0 * M * N * K / (row["fused_us"] * 1e-6) / 1e12, 1)
+            row["max_abs_diff_vs_dequant"] = round(
+                (outs["fused"].float() - outs["dequant"].float())
+                .abs().max().item(), 4)
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+            del graphs, outs
+        del qs, ds
+        torch.cuda.empty_cache()
+    return rows
+
+
+def main(*argv):
+    def opt(name, default):
+        return argv[argv.index(name) + 1].split(",") if name in argv \
+            else default
+
+    sites = opt("--sites", None)
+    ms = tuple(int(m) for m in opt("--ms", MS))
+    skip = {a for n in ("--sites", "--ms") if n in argv
+            for a in (n, argv[argv.index(n) + 1])}
+    out = next((a for a in argv if a not in skip), None)
+    rows = []
+    for s in SITES:
+        if sites is None or s[1] in sites:
+            rows += run_site(*s, ms)
+    if out:
+        with open(out, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
+if __name__ == "__main__":
+    main(*sys.argv[1:])

@@ -63,7 +63,18 @@ says: there is no "auto" rule, since going back to the bf16 weights would
 change the model. Every other site (T > 1, M > 64) runs ops.mx_dequantize
 into one scratch buffer sized for the largest weight, allocated once so a
 captured step can reuse it, then ops.linear (docs/KERNELS.md "Decode
-linears: MX weights")."""
+linears: MX weights"), unless mx_linear says otherwise.
+
+Those other MX sites (mx_linear=, or TEPDIST_MX_LINEAR): "dequant" (default)
+= the dequantize-then-ops.linear path above, unchanged. "fused" = every MX
+site the skinny MX kernel does not take runs ops.linear_mx, the LDS-tiled
+kernel that reads codes and scales as they lie, with the residual add and
+bias + gelu in its epilogue (Llama's gate and up are two calls and then
+ops.swiglu); a site it does not cover raises. "auto" = the same where the
+plan covers the site and hip.mx_gemm_auto has it measured ahead, the
+dequantize path elsewhere and on CPU. All three serve the same quantized
+model: only the order of the fp32 sums differs (docs/KERNELS.md "Prefill and
+large-batch linears: MX weights")."""
 
 from __future__ import annotations
 
@@ -87,7 +98,8 @@ class Generator:
                  decode_attn: Optional[str] = None,
                  decode_linear: Optional[str] = None,
                  prefill_attn: Optional[str] = None,
-                 weight_format: Optional[str] = None):
+                 weight_format: Optional[str] = None,
+                 mx_linear: Optional[str] = None):
         assert model.env.tp_size == 1, "generation engine: tp=1 layout"
         self.m = model
         self.cfg = model.cfg
@@ -123,6 +135,13 @@ class Generator:
                 f"weight_format must be 'bf16', 'mxfp8' or 'mxfp4', "
                 f"got {weight_format!r}")
         self.weight_format = weight_format
+        if mx_linear is None:
+            mx_linear = os.environ.get("TEPDIST_MX_LINEAR", "dequant")
+        if mx_linear not in ("dequant", "fused", "auto"):
+            raise ValueError(
+                f"mx_linear must be 'dequant', 'fused' or 'auto', "
+                f"got {mx_linear!r}")
+        self.mx_linear = mx_linear
         # id(parameter) -> its MXWeight; empty = serve the bf16 weights
         self.mxw = {}
         if weight_format != "bf16":
@@ -152,6 +171,28 @@ class Generator:
         from tepdist_amd.ops import hip
         return not hip.skinny_mx_why_not(
             x2, mw, hip.skinny_epi(bias, act, residual), mw_up, residual)
+
+    def _mx_fused(self, x2, mw, bias=None, act="none", residual=None) -> bool:
+        """Whether an MX site on x2 [M, K] that the skinny MX kernel left
+        runs ops.linear_mx. "dequant": never. "fused": always (on the GPU a
+        site the plan does not cover raises; on CPU it is the reference
+        op). "auto": on the GPU, where the plan covers the site and
+        hip.mx_gemm_auto has it measured ahead; never on CPU."""
+        if self.mx_linear == "dequant":
+            return False
+        if not x2.is_cuda:
+            return self.mx_linear == "fused"
+        from tepdist_amd.ops import hip
+        epi = hip.skinny_epi(bias, act, residual)
+        why = hip.mx_gemm_why_not(x2, mw, epi, residual)
+        if self.mx_linear == "fused":
+            if why:
+                raise ValueError(
+                    f"mx_linear='fused': site x{tuple(x2.shape)} w"
+                    f"{tuple(mw.shape)} is not covered: {why}")
+            return True
+        return not why and hip.mx_gemm_auto(
+            x2.shape[0], mw.shape[0], mw.shape[1], mx.bits(mw.fmt), epi)
 
     def _dequantized(self, mw, dtype):
         """bf16 weight of mw in the shared scratch buffer: valid until the
@@ -222,6 +263,10 @@ class Generator:
                 residual.reshape(-1, w.shape[0])
             if decode and self._mx_site(x2, mw, bias, act, r2):
                 y = ops.linear_decode_mx(x2, mw, bias, act, r2)
+                return y.reshape(*x.shape[:-1], w.shape[0]) \
+                    if residual is None else y.reshape(residual.shape)
+            if self._mx_fused(x2, mw, bias, act, r2):
+                y = ops.linear_mx(x2, mw, bias, act, r2)
                 return y.reshape(*x.shape[:-1], w.shape[0]) \
                     if residual is None else y.reshape(residual.shape)
             w = self._dequantized(mw, x.dtype)
@@ -332,6 +377,9 @@ class Generator:
         mg, mu = self.mxw.get(id(blk.w_gate)), self.mxw.get(id(blk.w_up))
         if mg is not None and T == 1 and self._mx_site(hn, mg, mw_up=mu):
             h = ops.swiglu_linear_decode_mx(hn, mg, mu)
+        elif mg is not None and self._mx_fused(hn, mg) \
+                and self._mx_fused(hn, mu):
+            h = ops.swiglu(ops.linear_mx(hn, mg), ops.linear_mx(hn, mu))
         elif mg is not None:    # one scratch buffer: gate, then up
             g = ops.linear(hn, self._dequantized(mg, hn.dtype))
             h = ops.swiglu(g, ops.linear(hn, self._dequantized(mu, hn.dtype)))

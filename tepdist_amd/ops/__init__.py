@@ -13,6 +13,7 @@ from tepdist_amd.ops.interface import (  # noqa: F401
     linear_decode,
     swiglu_linear_decode,
     linear_decode_mx,
+    linear_mx,
     swiglu_linear_decode_mx,
     mx_dequantize,
     sample_logits,

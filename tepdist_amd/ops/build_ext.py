@@ -30,6 +30,7 @@ SOURCES = [
     "prefill_attention.hip",
     "skinny_gemm.hip",
     "skinny_mx_gemm.hip",
+    "mx_gemm.hip",
     "sampling.hip",
     "moe_route.hip",
     "transpose.hip",
@@ -56,11 +57,14 @@ SOURCES = [
 # it (hipcc's -Xarch_device does not take options with arguments).
 # prefill_attention.hip takes the same flag: its softmax rescale and
 # epilogue would otherwise pair into v_pk_mul_f32. skinny_mx_gemm.hip shares
-# skinny_gemm.hip's LDS sum and epilogue, and its reason.
+# skinny_gemm.hip's LDS sum and epilogue, and its reason. mx_gemm.hip applies
+# the same fp32 epilogue (bias, residual, gelu_f) to four accumulator
+# elements at a time and is held to the same bits.
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
     "skinny_gemm.hip": _NO_PK_F32,
     "skinny_mx_gemm.hip": _NO_PK_F32,
+    "mx_gemm.hip": _NO_PK_F32,
     "prefill_attention.hip": _NO_PK_F32,
 }
 
@@ -83,6 +87,8 @@ def _needs_build() -> bool:
                                           CSRC / "gemm_plan.h",
                                           CSRC / "skinny_plan.h",
                                           CSRC / "skinny_mx_plan.h",
+                                          CSRC / "mx_gemm_plan.h",
+                                          CSRC / "mx_dequant.h",
                                           CSRC / "gemm_tile.h",
                                           CSRC / "rope_common.h",
                                           Path(__file__)]

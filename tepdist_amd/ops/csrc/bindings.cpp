@@ -13,6 +13,7 @@
 #include "common.h"
 #include "gemm_plan.h"
 #include "kernels.h"
+#include "mx_gemm_plan.h"
 #include "skinny_mx_plan.h"
 #include "skinny_plan.h"
 
@@ -147,6 +148,29 @@ PYBIND11_MODULE(_tepdist_hip, m) {
                        ldo, S(stream));
     check_launch();
   });
+
+  m.def("mx_gemm", [](uintptr_t x, uintptr_t codes, uintptr_t scales,
+                      uintptr_t bias, uintptr_t res, uintptr_t y, int M,
+                      int N, int K, int bits, int64_t ldx, int64_t ldc,
+                      int64_t lds, int64_t ldr, int64_t ldy, int epi,
+                      int tile, uintptr_t stream) {
+    mx_gemm(reinterpret_cast<void*>(x), reinterpret_cast<void*>(codes),
+            reinterpret_cast<void*>(scales), reinterpret_cast<void*>(bias),
+            reinterpret_cast<void*>(res), reinterpret_cast<void*>(y), M, N, K,
+            bits, ldx, ldc, lds, ldr, ldy, epi, tile, S(stream));
+    check_launch();
+  });
+
+  // (tile, stages, blocks, why_not) — host-only, no GPU
+  m.def("mx_gemm_plan", [](int M, int N, int K, int bits, int64_t ld_codes,
+                           int64_t ld_scales, int epi, int tile) {
+    const MxGemmPlan p =
+        mx_gemm_plan(M, N, K, bits, ld_codes, ld_scales, epi, tile);
+    return py::make_tuple(p.tile, p.stages, p.blocks,
+                          p.why_not ? p.why_not : "");
+  }, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("bits"),
+     py::arg("ld_codes"), py::arg("ld_scales"), py::arg("epi") = 0,
+     py::arg("tile") = 0);
 
   m.def("transpose", [](uintptr_t in, uintptr_t out, int R, int C,
                         int64_t si, int64_t so, int batch,

@@ -82,6 +82,18 @@ void mx_dequantize_bf16(const void* codes, const void* scales, void* out,
                         int N, int K, int bits, int64_t ldc, int64_t lds,
                         int64_t ldo, hipStream_t stream);
 
+// --- Tiled linear on MX weights (mx_gemm.hip) ---------------------------------
+// y[M, N] = epi(x[M, K] @ dq(W)[N, K]^T) for any M >= 1, K % 128 == 0: the
+// LDS-tiled kernel for the sites skinny_mx_gemm leaves (M > 64). Operands,
+// strides and epi as skinny_mx_gemm (no dual form); y has row stride ldy.
+// tile: 0 = mx_gemm_plan()'s choice, else 64 or 128. One launch, no
+// workspace, no atomics. Throws with mx_gemm_plan()'s reason when the call
+// is not covered.
+void mx_gemm(const void* x, const void* codes, const void* scales,
+             const void* bias, const void* res, void* y, int M, int N, int K,
+             int bits, int64_t ldx, int64_t ldc, int64_t lds, int64_t ldr,
+             int64_t ldy, int epi, int tile, hipStream_t stream);
+
 // --- Transpose -------------------------------------------------------------
 // out[c][r] = in[r][c] per batch (strides in elements).
 void transpose_bf16(const void* in, void* out, int R, int C,

@@ -335,6 +335,93 @@ def swiglu_linear_decode_mx(x, mw_gate, mw_up):
                       None, 0)
 
 
+# Linears of any M on MX weights (csrc/mx_gemm.hip): the LDS-tiled kernel for
+# the sites the skinny one leaves (prefill, chunks, decode batches above 64).
+# Coverage and tile come from csrc/mx_gemm_plan.h (ext.mx_gemm_plan).
+
+def mx_gemm_why_not(x: torch.Tensor, mw, epi: int = 0,
+                    residual: Optional[torch.Tensor] = None) -> str:
+    """'' when mx_gemm takes this call (x [M, K]), else why not."""
+    from tepdist_amd.ops import mx
+    ts = [t for t in (x, residual) if t is not None]
+    if any(t.dtype != BF16 or t.dim() != 2 or t.stride(1) != 1 for t in ts):
+        return "x and residual must be 2-D bf16 with a contiguous last dim"
+    M, K = x.shape
+    N = mw.shape[0]
+    if mw.shape[1] != K:
+        return "weight shape does not match x"
+    if residual is not None and tuple(residual.shape) != (M, N):
+        return "residual must be [M, N]"
+    mx.check(mw)
+    if mw.codes.stride(1) != 1 or mw.scales.stride(1) != 1 or \
+            not mw.codes.is_cuda or not mw.scales.is_cuda:
+        return "codes and scales must be device tensors with a " \
+               "contiguous last dim"
+    why = ext.mx_gemm_plan(M, N, K, mx.bits(mw.fmt), mw.codes.stride(0),
+                           mw.scales.stride(0), epi)[3]
+    if why:
+        return why
+    if mw.codes.data_ptr() % 16 or mw.scales.data_ptr() % 4:
+        return "codes need a 16-byte-aligned base, scales a " \
+               "4-byte-aligned one"
+    if x.data_ptr() % 16 or x.stride(0) % 8:
+        return "x needs a 16-byte-aligned base and rows"
+    return ""
+
+
+def _mx_gemm_raw(x, mw, bias, residual, epi, tile: int = 0, out=None):
+    """One mx_gemm launch on x [M, K]. tile: 0 = the plan's choice, else 64
+    or 128. out: a bf16 [M, N] view with a contiguous last dim to write."""
+    from tepdist_amd.ops import mx
+    why = mx_gemm_why_not(x, mw, epi, residual)
+    if why:
+        raise ValueError(f"linear_mx: not covered by the MX tiled kernel: "
+                         f"{why}")
+    M, K = x.shape
+    N = mw.shape[0]
+    if bias is not None:
+        assert bias.dtype == BF16 and bias.shape == (N,)
+        bias = bias.contiguous()
+    y = torch.empty(M, N, dtype=BF16, device=x.device) if out is None else out
+    assert y.dtype == BF16 and tuple(y.shape) == (M, N) and y.stride(1) == 1
+    ext.mx_gemm(x.data_ptr(), mw.codes.data_ptr(), mw.scales.data_ptr(),
+                _p(bias), _p(residual), y.data_ptr(), M, N, K,
+                mx.bits(mw.fmt), x.stride(0), mw.codes.stride(0),
+                mw.scales.stride(0),
+                residual.stride(0) if residual is not None else 0,
+                y.stride(0), epi, tile, _stream())
+    return y
+
+
+def linear_mx(x, mw, bias=None, act: str = "none", residual=None):
+    N = mw.shape[0]
+    x2 = x.reshape(-1, x.shape[-1])
+    r2 = None if residual is None else residual.reshape(-1, N)
+    y = _mx_gemm_raw(x2, mw, bias, r2, skinny_epi(bias, act, residual))
+    return y.reshape(*x.shape[:-1], N)
+
+
+def mx_gemm_auto(M: int, N: int, K: int, bits: int, epi: int) -> bool:
+    """Which covered sites the engine's mx_linear="auto" sends to mx_gemm:
+    those where the slowest window of ops.linear_mx beat the fastest window
+    of ops.mx_dequantize + ops.linear (plus the epilogue launches) in
+    profiles/linear_mx.json (docs/KERNELS.md "Prefill and large-batch
+    linears: MX weights"), measured at the ten flagship sites, M in {128,
+    256, 512, 1024, 2048, 4096}. The kernel wins while the output is small
+    (the 64-tile regime) and loses to the library's GEMM once M * N fills
+    the chip several times over. K < 4096: the heads (N >= 16384) up to
+    M = 256, every other site up to M * N = 2^22. K >= 4096 (down, out,
+    residual epilogue): M * N <= 2^20 from M = 512 (mxfp8) or 256 (mxfp4).
+    Between and beyond the measured M and shapes the rule extrapolates."""
+    if M <= 64:                     # the skinny MX kernel's range: not measured
+        return False
+    if K >= 4096:
+        return M * N <= 1 << 20 and M >= (512 if bits == 8 else 256)
+    if N >= 16384:
+        return M <= 256
+    return M * N <= 1 << 22
+
+
 def mx_dequantize(mw, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """bf16 [N, K] of an MXWeight, with the GEMM's conversion instructions.
     out: a bf16 [N, K] tensor with a contiguous last dim to write into."""

@@ -361,6 +361,21 @@ def linear_decode_mx(x, mw, bias=None, act: str = "none", residual=None):
     return _backend(x).linear_decode_mx(x, mw, bias, act, residual)
 
 
+def linear_mx(x, mw, bias=None, act: str = "none", residual=None):
+    """linear_decode_mx without its limit on the rows: x [..., K] with any
+    number of rows (prefill, a chunk, a large decode batch), residual
+    [..., N]; returns [..., N]. Same definition: the bf16 GEMM on the
+    dequantized weight, fp32 accumulation, bias, gelu and residual on the
+    fp32 sum, one rounding. On the GPU this is the LDS-tiled MX kernel
+    (csrc/mx_gemm.hip), which stages codes and scales as they lie and
+    dequantizes on the way to the MFMA: K a multiple of 128, code rows
+    16-byte and scale rows 4-byte aligned, x with 16-byte-aligned rows; a
+    call it does not cover raises ValueError with the reason. Inference
+    only."""
+    _no_backward("linear_mx", x, bias, residual)
+    return _backend(x).linear_mx(x, mw, bias, act, residual)
+
+
 def swiglu_linear_decode_mx(x, mw_gate, mw_up):
     """silu(x @ dq(mw_gate)^T) * (x @ dq(mw_up)^T) in one pass over both
     quantized weights (inference only). Coverage as linear_decode_mx; both

@@ -105,6 +105,12 @@ def linear_decode_mx(x: torch.Tensor, mw, bias=None, act: str = "none",
     return linear_decode(x, mx_dequantize(mw), bias, act, residual)
 
 
+def linear_mx(x: torch.Tensor, mw, bias=None, act: str = "none",
+              residual=None) -> torch.Tensor:
+    """linear_decode on the dequantized weight, x of any leading dims."""
+    return linear_decode(x, mx_dequantize(mw), bias, act, residual)
+
+
 def swiglu_linear_decode_mx(x: torch.Tensor, mw_gate, mw_up) -> torch.Tensor:
     """swiglu_linear_decode on the dequantized weights."""
     return swiglu_linear_decode(x, mx_dequantize(mw_gate),
