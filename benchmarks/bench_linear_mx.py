@@ -18,7 +18,19 @@ copy of the weight, sets * its weight bytes >= 512 MiB; median (min-max) of
 WINDOWS interleaved windows of REPLAYS replays. `wins`: the slowest "fused"
 window beats the fastest "dequant" window.
 
-    bench_linear_mx.py [out.json] [--sites qkv,o] [--ms 128,512]"""
+    bench_linear_mx.py [out.json] [--sites qkv,o] [--ms 128,512]
+
+--act mxfp8: the MXFP8-activation model instead (ops.linear_mx_a8, csrc/
+mx_gemm_a8.hip), same sites, M and method. Contenders:
+  "quant_a8" ops.mx_quantize_act + ops.linear_mx_a8 (the SwiGLU site: one
+             quantization, two calls, ops.swiglu), as the engine runs it;
+  "a8"       ops.linear_mx_a8 on x quantized beforehand: the GEMM alone;
+  "library"  the same model on the library: ops.mx_quantize_act(roundtrip) +
+             ops.mx_dequantize + ops.linear and the engine's tail launches;
+  "w_fused", "w_dequant"  from M = 2048, for information: the weight-only
+             paths on bf16 x (ops.linear_mx; dequantize + ops.linear), a
+             different model.
+`wins`: the slowest "quant_a8" window beats the fastest "library" window."""
 import json
 import os
 import statistics
@@ -117,6 +129,85 @@ def run_site(model, site, N, K, form, ms):
     return rows
 
 
+def run_site_a8(model, site, N, K, form, ms):
+    torch.manual_seed(0)
+    nmat = 2 if form == "swiglu" else 1
+    w = [torch.randn(N, K, dtype=BF16, device="cuda") * K ** -0.5
+         for _ in range(nmat)]
+    b = torch.randn(N, dtype=BF16, device="cuda")
+    scratch = torch.empty(N, K, dtype=BF16, device="cuda")
+    rows = []
+    for fmt in mx.FORMATS:
+        q = [ops.mx_quantize(t, fmt) for t in w]
+        nbytes = nmat * q[0].nbytes
+        sets = max(4, -(-COLD_BYTES // nbytes))
+        qs = [[mx.MXWeight(m.codes.clone(), m.scales.clone(), m.fmt, m.shape)
+               for _ in range(sets)] for m in q]
+        for M in ms:
+            x = torch.randn(M, K, dtype=BF16, device="cuda")
+            r = torch.randn(M, N, dtype=BF16, device="cuda")
+            xq, xr = ops.mx_quantize_act(x), torch.empty_like(x)
+            bias = b if "bias" in form else None
+            res = r if "res" in form else None
+            act = "gelu" if form == "bias_gelu" else "none"
+            epi = hip.skinny_epi(bias, act, res)
+
+            def tail(ys):
+                if nmat == 2:
+                    return ops.swiglu(ys[0], ys[1])
+                return ys[0] if res is None else res + ys[0]
+
+            def a8(xin, i):
+                if nmat == 2:
+                    return ops.swiglu(*(hip._mx_gemm_a8_raw(
+                        xin, a[i], None, None, 0) for a in qs))
+                return hip._mx_gemm_a8_raw(xin, qs[0][i], bias, res, epi)
+
+            fns = {
+                "quant_a8": lambda i: a8(ops.mx_quantize_act(x, out=xq), i),
+                "a8": lambda i: a8(xq, i),
+                "library": lambda i: tail([ops.linear(
+                    ops.mx_quantize_act(x, roundtrip=True, out=xr),
+                    ops.mx_dequantize(a[i], out=scratch), bias, act)
+                    for a in qs]),
+            }
+            if M >= 2048:
+                fns["w_fused"] = lambda i: ops.swiglu(*(hip._mx_gemm_raw(
+                    x, a[i], None, None, 0) for a in qs)) if nmat == 2 \
+                    else hip._mx_gemm_raw(x, qs[0][i], bias, res, epi)
+                fns["w_dequant"] = lambda i: tail([ops.linear(
+                    x, ops.mx_dequantize(a[i], out=scratch), bias, act)
+                    for a in qs])
+            graphs, outs = {}, {}
+            for name, fn in fns.items():
+                graphs[name], outs[name] = capture(fn, sets)
+            t = {k: [] for k in graphs}
+            for _ in range(WINDOWS):
+                for k, g in graphs.items():
+                    t[k].append(window_us(g, sets))
+            tile = hip.ext.mx_gemm_a8_plan(
+                M, N, K, mx.bits(fmt), q[0].codes.stride(0),
+                q[0].scales.stride(0), K, K // 32)[0]
+            row = {"bench": "linear_mx_a8", "model": model, "site": site,
+                   "form": form, "fmt": fmt, "M": M, "N": N, "K": K,
+                   "tile": tile, "sets": sets, "weight_bytes": nbytes}
+            for k, v in t.items():
+                row[f"{k}_us"] = round(statistics.median(v), 2)
+                row[f"{k}_us_min_max"] = [round(min(v), 2), round(max(v), 2)]
+            row["wins"] = max(t["quant_a8"]) < min(t["library"])
+            row["a8_tflops"] = round(
+                nmat * 2.0 * M * N * K / (row["a8_us"] * 1e-6) / 1e12, 1)
+            row["max_abs_diff_vs_library"] = round(
+                (outs["quant_a8"].float() - outs["library"].float())
+                .abs().max().item(), 4)
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+            del graphs, outs
+        del qs
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main(*argv):
     def opt(name, default):
         return argv[argv.index(name) + 1].split(",") if name in argv \
@@ -124,13 +215,16 @@ def main(*argv):
 
     sites = opt("--sites", None)
     ms = tuple(int(m) for m in opt("--ms", MS))
-    skip = {a for n in ("--sites", "--ms") if n in argv
+    act = opt("--act", ["bf16"])[0]
+    if act not in ("bf16", "mxfp8"):
+        raise SystemExit(f"--act must be bf16 or mxfp8, got {act!r}")
+    skip = {a for n in ("--sites", "--ms", "--act") if n in argv
             for a in (n, argv[argv.index(n) + 1])}
     out = next((a for a in argv if a not in skip), None)
     rows = []
     for s in SITES:
         if sites is None or s[1] in sites:
-            rows += run_site(*s, ms)
+            rows += (run_site_a8 if act == "mxfp8" else run_site)(*s, ms)
     if out:
         with open(out, "w") as f:
             json.dump(rows, f, indent=1)

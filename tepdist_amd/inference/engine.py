@@ -74,7 +74,22 @@ ops.swiglu); a site it does not cover raises. "auto" = the same where the
 plan covers the site and hip.mx_gemm_auto has it measured ahead, the
 dequantize path elsewhere and on CPU. All three serve the same quantized
 model: only the order of the fp32 sums differs (docs/KERNELS.md "Prefill and
-large-batch linears: MX weights")."""
+large-batch linears: MX weights").
+
+Activation format (act_format=, or TEPDIST_ACT_FORMAT): "bf16" (default) =
+every path above as it was. "mxfp8" = W4A8 / W8A8: the input of every
+quantized linear (quantized_params) is quantized to MXFP8 by the rule of
+ops/mx.py, at every site and every T, so prefill and decode serve one model,
+and it is a different model from the weight-only one. It needs a
+weight_format other than "bf16" and mx_linear left at its default. Sites of
+T > 1 or M > 64 run ops.linear_mx_a8, the scaled-MFMA kernel that multiplies
+codes by codes (Llama's gate and up share one ops.mx_quantize_act of the
+normed input, then ops.swiglu); a site its plan refuses raises. Single-token
+sites the skinny MX plan covers run ops.mx_quantize_act(x, roundtrip=True)
+into a buffer allocated once, then ops.linear_decode_mx /
+ops.swiglu_linear_decode_mx as before: the same values, only the order of
+the fp32 sum differs. There is no "auto" rule yet (docs/KERNELS.md "MX
+weights x MXFP8 activations")."""
 
 from __future__ import annotations
 
@@ -99,7 +114,8 @@ class Generator:
                  decode_linear: Optional[str] = None,
                  prefill_attn: Optional[str] = None,
                  weight_format: Optional[str] = None,
-                 mx_linear: Optional[str] = None):
+                 mx_linear: Optional[str] = None,
+                 act_format: Optional[str] = None):
         assert model.env.tp_size == 1, "generation engine: tp=1 layout"
         self.m = model
         self.cfg = model.cfg
@@ -142,6 +158,18 @@ class Generator:
                 f"mx_linear must be 'dequant', 'fused' or 'auto', "
                 f"got {mx_linear!r}")
         self.mx_linear = mx_linear
+        if act_format is None:
+            act_format = os.environ.get("TEPDIST_ACT_FORMAT", "bf16")
+        if act_format not in ("bf16", "mxfp8"):
+            raise ValueError(
+                f"act_format must be 'bf16' or 'mxfp8', got {act_format!r}")
+        if act_format == "mxfp8" and (weight_format == "bf16"
+                                      or mx_linear != "dequant"):
+            raise ValueError(
+                "act_format='mxfp8' needs an MX weight_format and mx_linear "
+                f"at its default, got weight_format={weight_format!r}, "
+                f"mx_linear={mx_linear!r}")
+        self.act_format = act_format
         # id(parameter) -> its MXWeight; empty = serve the bf16 weights
         self.mxw = {}
         if weight_format != "bf16":
@@ -149,6 +177,10 @@ class Generator:
             self.mxw = {id(w): mx.mx_quantize(w, weight_format) for w in ws}
             self._dq = torch.empty(max(w.numel() for w in ws),
                                    dtype=torch.bfloat16, device=ws[0].device)
+            if act_format == "mxfp8":   # round trip of a single-token input
+                self._xr = torch.empty(64 * max(w.shape[1] for w in ws),
+                                       dtype=torch.bfloat16,
+                                       device=ws[0].device)
 
     @staticmethod
     def quantized_params(model):
@@ -193,6 +225,15 @@ class Generator:
             return True
         return not why and hip.mx_gemm_auto(
             x2.shape[0], mw.shape[0], mw.shape[1], mx.bits(mw.fmt), epi)
+
+    def _roundtrip(self, x2):
+        """The MXFP8 round trip of x2 [M, K] in the buffer of the
+        single-token sites (M <= 64 there): valid until the next call."""
+        M, K = x2.shape
+        out = self._xr[:M * K].view(M, K) \
+            if M * K <= self._xr.numel() and x2.dtype == self._xr.dtype \
+            else None
+        return ops.mx_quantize_act(x2, roundtrip=True, out=out)
 
     def _dequantized(self, mw, dtype):
         """bf16 weight of mw in the shared scratch buffer: valid until the
@@ -261,6 +302,14 @@ class Generator:
             x2 = x.reshape(-1, x.shape[-1])
             r2 = None if residual is None else \
                 residual.reshape(-1, w.shape[0])
+            if self.act_format == "mxfp8":
+                if decode and self._mx_site(x2, mw, bias, act, r2):
+                    y = ops.linear_decode_mx(self._roundtrip(x2), mw, bias,
+                                             act, r2)
+                else:
+                    y = ops.linear_mx_a8(x2, mw, bias, act, r2)
+                return y.reshape(*x.shape[:-1], w.shape[0]) \
+                    if residual is None else y.reshape(residual.shape)
             if decode and self._mx_site(x2, mw, bias, act, r2):
                 y = ops.linear_decode_mx(x2, mw, bias, act, r2)
                 return y.reshape(*x.shape[:-1], w.shape[0]) \
@@ -375,7 +424,14 @@ class Generator:
         B, T, d = x.shape
         hn = ops.rmsnorm(x.reshape(B * T, d), blk.ln2_g, cfg.rms_eps)
         mg, mu = self.mxw.get(id(blk.w_gate)), self.mxw.get(id(blk.w_up))
-        if mg is not None and T == 1 and self._mx_site(hn, mg, mw_up=mu):
+        if mg is not None and self.act_format == "mxfp8":
+            if T == 1 and self._mx_site(hn, mg, mw_up=mu):
+                h = ops.swiglu_linear_decode_mx(self._roundtrip(hn), mg, mu)
+            else:               # one quantization, shared by gate and up
+                xq = ops.mx_quantize_act(hn)
+                h = ops.swiglu(ops.linear_mx_a8(xq, mg),
+                               ops.linear_mx_a8(xq, mu))
+        elif mg is not None and T == 1 and self._mx_site(hn, mg, mw_up=mu):
             h = ops.swiglu_linear_decode_mx(hn, mg, mu)
         elif mg is not None and self._mx_fused(hn, mg) \
                 and self._mx_fused(hn, mu):

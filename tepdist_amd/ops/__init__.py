@@ -14,6 +14,8 @@ from tepdist_amd.ops.interface import (  # noqa: F401
     swiglu_linear_decode,
     linear_decode_mx,
     linear_mx,
+    linear_mx_a8,
+    mx_quantize_act,
     swiglu_linear_decode_mx,
     mx_dequantize,
     sample_logits,

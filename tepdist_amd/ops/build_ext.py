@@ -31,6 +31,8 @@ SOURCES = [
     "skinny_gemm.hip",
     "skinny_mx_gemm.hip",
     "mx_gemm.hip",
+    "mx_gemm_a8.hip",
+    "mx_act_quant.hip",
     "sampling.hip",
     "moe_route.hip",
     "transpose.hip",
@@ -59,12 +61,14 @@ SOURCES = [
 # epilogue would otherwise pair into v_pk_mul_f32. skinny_mx_gemm.hip shares
 # skinny_gemm.hip's LDS sum and epilogue, and its reason. mx_gemm.hip applies
 # the same fp32 epilogue (bias, residual, gelu_f) to four accumulator
-# elements at a time and is held to the same bits.
+# elements at a time and is held to the same bits, and mx_gemm_a8.hip has
+# that epilogue line for line.
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
     "skinny_gemm.hip": _NO_PK_F32,
     "skinny_mx_gemm.hip": _NO_PK_F32,
     "mx_gemm.hip": _NO_PK_F32,
+    "mx_gemm_a8.hip": _NO_PK_F32,
     "prefill_attention.hip": _NO_PK_F32,
 }
 
@@ -88,6 +92,7 @@ def _needs_build() -> bool:
                                           CSRC / "skinny_plan.h",
                                           CSRC / "skinny_mx_plan.h",
                                           CSRC / "mx_gemm_plan.h",
+                                          CSRC / "mx_gemm_a8_plan.h",
                                           CSRC / "mx_dequant.h",
                                           CSRC / "gemm_tile.h",
                                           CSRC / "rope_common.h",

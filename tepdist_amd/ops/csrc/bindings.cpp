@@ -4,15 +4,19 @@
 // This keeps the extension a pure hipcc build (no hipify, no libtorch ABI).
 
 #include <pybind11/pybind11.h>
+#include <pybind11/stl.h>
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "common.h"
 #include "gemm_plan.h"
 #include "kernels.h"
+#include "mx_gemm_a8_plan.h"
 #include "mx_gemm_plan.h"
 #include "skinny_mx_plan.h"
 #include "skinny_plan.h"
@@ -171,6 +175,57 @@ PYBIND11_MODULE(_tepdist_hip, m) {
   }, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("bits"),
      py::arg("ld_codes"), py::arg("ld_scales"), py::arg("epi") = 0,
      py::arg("tile") = 0);
+
+  // out != 0: the round-trip (dequantized bf16), codes and scales 0
+  m.def("mx_act_quant", [](uintptr_t x, uintptr_t codes, uintptr_t scales,
+                           uintptr_t out, int M, int K, int64_t ldx,
+                           int64_t ldc, int64_t lds, int64_t ldo,
+                           uintptr_t stream) {
+    mx_act_quant(reinterpret_cast<void*>(x), reinterpret_cast<void*>(codes),
+                 reinterpret_cast<void*>(scales),
+                 reinterpret_cast<void*>(out), M, K, ldx, ldc, lds, ldo,
+                 S(stream));
+    check_launch();
+  });
+
+  // the quantizer's rule on the host: (scale byte, e4m3 codes) of one block
+  // of bf16 bit patterns — the lines the kernel runs, no GPU
+  m.def("mx_act_quant_block", [](const std::vector<unsigned>& bits) {
+    unsigned amax = 0;
+    for (unsigned b : bits) amax = std::max(amax, b & 0x7fffu);
+    const unsigned byte = mxq_scale_byte(amax);
+    std::vector<unsigned> codes;
+    for (unsigned b : bits) codes.push_back(mxq_e4m3(b & 0xffffu, byte));
+    return py::make_tuple(byte, codes);
+  });
+
+  m.def("mx_gemm_a8", [](uintptr_t xcodes, uintptr_t xscales, uintptr_t codes,
+                         uintptr_t scales, uintptr_t bias, uintptr_t res,
+                         uintptr_t y, int M, int N, int K, int bits,
+                         int64_t ldxc, int64_t ldxs, int64_t ldc, int64_t lds,
+                         int64_t ldr, int64_t ldy, int epi, int tile,
+                         uintptr_t stream) {
+    mx_gemm_a8(reinterpret_cast<void*>(xcodes),
+               reinterpret_cast<void*>(xscales),
+               reinterpret_cast<void*>(codes), reinterpret_cast<void*>(scales),
+               reinterpret_cast<void*>(bias), reinterpret_cast<void*>(res),
+               reinterpret_cast<void*>(y), M, N, K, bits, ldxc, ldxs, ldc,
+               lds, ldr, ldy, epi, tile, S(stream));
+    check_launch();
+  });
+
+  // (tile, stages, blocks, why_not) — host-only, no GPU
+  m.def("mx_gemm_a8_plan", [](int M, int N, int K, int bits,
+                              int64_t ld_wcodes, int64_t ld_wscales,
+                              int64_t ld_xcodes, int64_t ld_xscales, int epi,
+                              int tile) {
+    const MxGemmPlan p = mx_gemm_a8_plan(M, N, K, bits, ld_wcodes, ld_wscales,
+                                         ld_xcodes, ld_xscales, epi, tile);
+    return py::make_tuple(p.tile, p.stages, p.blocks,
+                          p.why_not ? p.why_not : "");
+  }, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("bits"),
+     py::arg("ld_wcodes"), py::arg("ld_wscales"), py::arg("ld_xcodes"),
+     py::arg("ld_xscales"), py::arg("epi") = 0, py::arg("tile") = 0);
 
   m.def("transpose", [](uintptr_t in, uintptr_t out, int R, int C,
                         int64_t si, int64_t so, int batch,

@@ -422,6 +422,136 @@ def mx_gemm_auto(M: int, N: int, K: int, bits: int, epi: int) -> bool:
     return M * N <= 1 << 22
 
 
+# MX weights x MXFP8 activations (csrc/mx_act_quant.hip, csrc/mx_gemm_a8.hip):
+# the activation quantizer and the GEMM on the scaled MFMA, which reads both
+# operands as codes and scale bytes. Coverage and tile come from
+# csrc/mx_gemm_a8_plan.h (ext.mx_gemm_a8_plan).
+
+def mx_quantize_act(x: torch.Tensor, roundtrip: bool = False, out=None):
+    """x [..., K] bf16 (K % 32 == 0, rows strided, last dim contiguous)
+    quantized as mx.mx_quantize(x, "mxfp8"), bit for bit, in one launch.
+    roundtrip=False: an MXWeight(codes [M, K], scales [M, K / 32], "mxfp8",
+    (M, K)) with M the product of the leading dims; out = such an MXWeight to
+    write into (uint8 views, last dim contiguous). roundtrip=True: the
+    dequantized values as bf16 of x's shape; out = a bf16 tensor of x's shape
+    whose rows flatten to [M, K] as a view."""
+    from tepdist_amd.ops import mx
+    K = x.shape[-1] if x.dim() else 0
+    if x.dtype != BF16 or x.dim() < 1 or K < 32 or K % 32 or not x.is_cuda \
+            or x.stride(-1) != 1:
+        raise ValueError("mx_quantize_act: x must be a bf16 device tensor "
+                         "[..., K] with K a positive multiple of 32 and a "
+                         "contiguous last dim")
+    x2 = x.reshape(-1, K)   # a view for row-strided 2-D x, else may copy
+    M = x2.shape[0]
+    if x2.data_ptr() % 16 or x2.stride(0) % 8:
+        raise ValueError("mx_quantize_act: x needs a 16-byte-aligned base "
+                         "and rows")
+    if roundtrip:
+        if out is None:
+            out = torch.empty(x.shape, dtype=BF16, device=x.device)
+        o2 = out.view(-1, K) if out.dim() != 2 else out
+        if out.dtype != BF16 or out.shape != x.shape or o2.stride(1) != 1 \
+                or o2.data_ptr() % 16 or o2.stride(0) % 8:
+            raise ValueError("mx_quantize_act: out must be bf16 of x's shape "
+                             "with a 16-byte-aligned base and rows")
+        ext.mx_act_quant(x2.data_ptr(), 0, 0, o2.data_ptr(), M, K,
+                         x2.stride(0), 0, 0, o2.stride(0), _stream())
+        return out
+    if out is None:
+        out = mx.MXWeight(
+            torch.empty(M, K, dtype=torch.uint8, device=x.device),
+            torch.empty(M, K // 32, dtype=torch.uint8, device=x.device),
+            "mxfp8", (M, K))
+    c, s = out.codes, out.scales
+    if out.fmt != "mxfp8" or tuple(out.shape) != (M, K) or \
+            mx.check(out) != (M, K) or c.stride(1) != 1 or s.stride(1) != 1 \
+            or not c.is_cuda or not s.is_cuda or c.data_ptr() % 8 or \
+            c.stride(0) % 8:
+        raise ValueError(f"mx_quantize_act: out must be an mxfp8 MXWeight of "
+                         f"shape {(M, K)} on the device with 8-byte-aligned "
+                         "code rows")
+    ext.mx_act_quant(x2.data_ptr(), c.data_ptr(), s.data_ptr(), 0, M, K,
+                     x2.stride(0), c.stride(0), s.stride(0), 0, _stream())
+    return out
+
+
+def mx_gemm_a8_why_not(xq, mw, epi: int = 0,
+                       residual: Optional[torch.Tensor] = None) -> str:
+    """'' when mx_gemm_a8 takes this call (xq an "mxfp8" MXWeight [M, K]),
+    else why not."""
+    from tepdist_amd.ops import mx
+    if residual is not None and (residual.dtype != BF16 or residual.dim() != 2
+                                 or residual.stride(1) != 1):
+        return "residual must be 2-D bf16 with a contiguous last dim"
+    if xq.fmt != "mxfp8":
+        return "activations must be mxfp8"
+    M, K = xq.shape
+    N = mw.shape[0]
+    if mw.shape[1] != K:
+        return "weight shape does not match x"
+    if residual is not None and tuple(residual.shape) != (M, N):
+        return "residual must be [M, N]"
+    for w in (xq, mw):
+        mx.check(w)
+        if w.codes.stride(1) != 1 or w.scales.stride(1) != 1 or \
+                not w.codes.is_cuda or not w.scales.is_cuda:
+            return "codes and scales must be device tensors with a " \
+                   "contiguous last dim"
+    why = ext.mx_gemm_a8_plan(M, N, K, mx.bits(mw.fmt), mw.codes.stride(0),
+                              mw.scales.stride(0), xq.codes.stride(0),
+                              xq.scales.stride(0), epi)[3]
+    if why:
+        return why
+    for w in (xq, mw):
+        if w.codes.data_ptr() % 16 or w.scales.data_ptr() % 4:
+            return "codes need a 16-byte-aligned base, scales a " \
+                   "4-byte-aligned one"
+    return ""
+
+
+def _mx_gemm_a8_raw(xq, mw, bias, residual, epi, tile: int = 0, out=None):
+    """One mx_gemm_a8 launch on quantized activations xq [M, K]. tile: 0 =
+    the plan's choice, else 64 or 128. out: a bf16 [M, N] view with a
+    contiguous last dim to write."""
+    from tepdist_amd.ops import mx
+    why = mx_gemm_a8_why_not(xq, mw, epi, residual)
+    if why:
+        raise ValueError(f"linear_mx_a8: not covered by the scaled-MFMA "
+                         f"kernel: {why}")
+    M, K = xq.shape
+    N = mw.shape[0]
+    dev = xq.codes.device
+    if bias is not None:
+        assert bias.dtype == BF16 and bias.shape == (N,)
+        bias = bias.contiguous()
+    y = torch.empty(M, N, dtype=BF16, device=dev) if out is None else out
+    assert y.dtype == BF16 and tuple(y.shape) == (M, N) and y.stride(1) == 1
+    ext.mx_gemm_a8(xq.codes.data_ptr(), xq.scales.data_ptr(),
+                   mw.codes.data_ptr(), mw.scales.data_ptr(), _p(bias),
+                   _p(residual), y.data_ptr(), M, N, K, mx.bits(mw.fmt),
+                   xq.codes.stride(0), xq.scales.stride(0),
+                   mw.codes.stride(0), mw.scales.stride(0),
+                   residual.stride(0) if residual is not None else 0,
+                   y.stride(0), epi, tile, _stream())
+    return y
+
+
+def linear_mx_a8(x, mw, bias=None, act: str = "none", residual=None):
+    from tepdist_amd.ops import mx
+    N = mw.shape[0]
+    if isinstance(x, mx.MXWeight):
+        xq, lead = x, x.shape[:1]
+    else:
+        if x.shape[-1] % 128:   # before the quantizer's weaker K % 32
+            raise ValueError("linear_mx_a8: not covered by the scaled-MFMA "
+                             "kernel: K must be a positive multiple of 128")
+        xq, lead = mx_quantize_act(x), x.shape[:-1]
+    r2 = None if residual is None else residual.reshape(-1, N)
+    y = _mx_gemm_a8_raw(xq, mw, bias, r2, skinny_epi(bias, act, residual))
+    return y.reshape(*lead, N)
+
+
 def mx_dequantize(mw, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """bf16 [N, K] of an MXWeight, with the GEMM's conversion instructions.
     out: a bf16 [N, K] tensor with a contiguous last dim to write into."""

@@ -376,6 +376,37 @@ def linear_mx(x, mw, bias=None, act: str = "none", residual=None):
     return _backend(x).linear_mx(x, mw, bias, act, residual)
 
 
+def mx_quantize_act(x, roundtrip: bool = False, out=None):
+    """MXFP8 quantization of activations x [..., K] (bf16, K a multiple of
+    32) by the rule of ops.mx_quantize(x, "mxfp8"), bit for bit: one e8m0
+    scale byte per 32 k, e4m3 elements. roundtrip=False returns an
+    ops.mx.MXWeight of shape (M, K), M the product of the leading dims;
+    roundtrip=True the dequantized values as a tensor like x (exact in bf16).
+    out: the MXWeight or tensor to write into, so a captured step allocates
+    nothing. On the GPU one HIP launch (csrc/mx_act_quant.hip): rows may be
+    strided, 16-byte aligned. Inference only."""
+    _no_backward("mx_quantize_act", x)
+    return _backend(x).mx_quantize_act(x, roundtrip, out)
+
+
+def linear_mx_a8(x, mw, bias=None, act: str = "none", residual=None):
+    """linear_mx with MXFP8 activations (W4A8 / W8A8): x is a bf16 tensor
+    [..., K], quantized by mx_quantize_act in one launch, or an activation
+    MXWeight [M, K] from it (shared by several linears). The result is
+    defined in fp64 as dq(Xq) . dq(W)^T + bias + residual, then act, rounded
+    once to bf16; it is computed with fp32 accumulation. This is a different
+    model from linear_mx on the same x: the activations are rounded to e4m3
+    blocks. On the GPU this is the scaled-MFMA kernel (csrc/mx_gemm_a8.hip),
+    which multiplies codes by codes and never dequantizes either operand: K
+    a multiple of 128, code rows 16-byte and scale rows 4-byte aligned on
+    both sides; a call it does not cover raises ValueError with the reason.
+    Inference only."""
+    from tepdist_amd.ops.mx import MXWeight
+    t = x.codes if isinstance(x, MXWeight) else x
+    _no_backward("linear_mx_a8", t, bias, residual)
+    return _backend(t).linear_mx_a8(x, mw, bias, act, residual)
+
+
 def swiglu_linear_decode_mx(x, mw_gate, mw_up):
     """silu(x @ dq(mw_gate)^T) * (x @ dq(mw_up)^T) in one pass over both
     quantized weights (inference only). Coverage as linear_decode_mx; both

@@ -111,6 +111,30 @@ def linear_mx(x: torch.Tensor, mw, bias=None, act: str = "none",
     return linear_decode(x, mx_dequantize(mw), bias, act, residual)
 
 
+def mx_quantize_act(x: torch.Tensor, roundtrip: bool = False, out=None):
+    """mx.mx_quantize(x, "mxfp8") on x [..., K] flattened to [M, K]; with
+    roundtrip its mx.dequantize_ref in x's shape and dtype."""
+    from tepdist_amd.ops import mx
+    q = mx.mx_quantize(x.reshape(-1, x.shape[-1]), "mxfp8")
+    if roundtrip:
+        d = mx.dequantize_ref(q).to(x.dtype).reshape(x.shape)
+        return d if out is None else out.copy_(d)
+    if out is not None:
+        out.codes.copy_(q.codes)
+        out.scales.copy_(q.scales)
+        return out
+    return q
+
+
+def linear_mx_a8(x, mw, bias=None, act: str = "none", residual=None):
+    """linear_mx on the MXFP8 round trip of x (a tensor, or an activation
+    MXWeight [M, K], whose result is bf16)."""
+    from tepdist_amd.ops import mx
+    xd = mx.dequantize_ref(x) if isinstance(x, mx.MXWeight) else \
+        mx_quantize_act(x, roundtrip=True)
+    return linear_mx(xd, mw, bias, act, residual)
+
+
 def swiglu_linear_decode_mx(x: torch.Tensor, mw_gate, mw_up) -> torch.Tensor:
     """swiglu_linear_decode on the dequantized weights."""
     return swiglu_linear_decode(x, mx_dequantize(mw_gate),
