@@ -10,9 +10,10 @@ config is a GPT-2 or Llama config name (e.g. gpt2-345m, llama-1b-gqa).
 With modes given (e.g. `fused composed fused composed`) the model is built
 once and the modes are measured in that order in this process, which is how
 to compare them: alternating, in one GPU visit. A mode is `attn` or
-`attn:linear` or `attn:linear:weights` (e.g. `auto:gemm auto:auto auto:gemm
-auto:auto`, or `auto:auto:bf16 auto:auto:mxfp4` for the weight formats of
-the engine's weight_format); a part left out or empty keeps the
+`attn:linear` or `attn:linear:weights` or `attn:linear:weights:kv` (e.g.
+`auto:gemm auto:auto auto:gemm auto:auto`, `auto:auto:bf16 auto:auto:mxfp4`
+for the weight formats of the engine's weight_format, or `auto:::bf16
+auto:::mxfp8` for its kv_format); a part left out or empty keeps the
 environment's choice."""
 import json
 import os
@@ -40,9 +41,9 @@ def build_model(name):
 
 
 def measure(cfg, m, name, mode=None, batch=32, prompt=512, new=128):
-    attn, lin, wfmt = ((mode or "").split(":") + ["", ""])[:3]
+    attn, lin, wfmt, kv = ((mode or "").split(":") + ["", "", ""])[:4]
     g = Generator(m, decode_attn=attn or None, decode_linear=lin or None,
-                  weight_format=wfmt or None)
+                  weight_format=wfmt or None, kv_format=kv or None)
     gen = torch.Generator().manual_seed(0)
     ids = torch.randint(0, cfg.vocab_size, (batch, prompt),
                         generator=gen).cuda()
@@ -67,6 +68,11 @@ def measure(cfg, m, name, mode=None, batch=32, prompt=512, new=128):
         "decode_attn": g.decode_attn,
         "decode_linear": g.decode_linear,
         "weight_format": g.weight_format,
+        "kv_format": g.kv_format,
+        "kv_cache_bytes": sum(
+            c.nbytes if hasattr(c, "codes") else c.numel() * c.element_size()
+            for cs in g.new_caches(batch, prompt + new, "meta",
+                                   torch.bfloat16) for c in cs),
         "decode_attn_fused": g._fused_decode(
             out.new_empty(0, dtype=torch.bfloat16),
             cfg.n_embd // cfg.n_head, cfg.n_head // g.kv_heads),

@@ -11,7 +11,8 @@ layer's cache) does not sit in the 256 MiB Infinity Cache at the default
 shape — and timed with device events over REPLAYS replays per window,
 WINDOWS windows per variant, fused and composed windows interleaved.
 Prints one JSON line per (shape, position) and one per splits-sweep
-point.
+point. Mode "kv8" compares the bf16-cache kernel with the MXFP8-cache kernel
+instead (profiles/decode_attention_kv8.json).
 
 The achieved-bandwidth figure divides the bytes the algorithm needs — the
 valid K and V rows, (p + 1) * D * 2 B each per (b, h); q/out/new rows are
@@ -304,6 +305,80 @@ def main_gqa():
     run_gqa_shape(32, 32, 4, 128, 640, (639,), sweep=True, mha=False)
 
 
+# -- MXFP8 KV cache (mode "kv8") ---------------------------------------------
+#
+# The bf16-cache kernel against the MX-cache kernel (decode_attention_mx.hip)
+# on the same shape, position and split count, at the shapes of both tables
+# above. needed bytes of the MX cache: codes plus scale bytes of the valid
+# rows. A win is the slowest MX window beating the fastest bf16 one.
+
+def run_kv8_shape(B, H, Hkv, D, S_max, positions, rope, sweep=False):
+    from tepdist_amd.ops import mx
+    theta = THETA if rope else None
+    for p in positions:
+        kc, vc, _, _, qkv, cur_t, _ = make_gqa_case(B, H, Hkv, D, S_max, p,
+                                                    False)
+        km, vm = [], []
+        for src, dst in ((kc, km), (vc, vm)):
+            for t in src:
+                w = mx.mx_quantize(t.reshape(-1, D), "mxfp8")
+                dst.append(mx.MXCache(w.codes.view(B, Hkv, S_max, D),
+                                      w.scales.view(B, Hkv, S_max, D // 32)))
+        q, k, v = _views(qkv, B, H, Hkv, D)
+
+        def fn(ck, cv, splits):
+            return lambda i: ops.decode_attention(
+                q, ck[i], cv[i], cur_t, k_new=k, v_new=v, splits=splits,
+                rope_theta=theta)
+        auto = hip.decode_splits(B * Hkv, S_max, H // Hkv)
+        r = time_alternating({"bf16": capture(fn(kc, vc, auto))[0],
+                              "mxfp8": capture(fn(km, vm, auto))[0]})
+        nb = needed_bytes(B, Hkv, D, p)
+        nb8 = 2 * B * Hkv * (p + 1) * (D + D // 32)
+        row = {"bench": "decode_attn_kv8", "B": B, "H": H, "Hkv": Hkv,
+               "G": H // Hkv, "D": D, "S_max": S_max, "pos": p,
+               "rope": rope, "splits": auto, "needed_kv_bytes_bf16": nb,
+               "needed_kv_bytes_mxfp8": nb8,
+               "bf16_bytes_per_s": round(nb / (r["bf16"][0] * 1e-6), 0),
+               "mxfp8_bytes_per_s": round(nb8 / (r["mxfp8"][0] * 1e-6), 0),
+               "speedup": round(r["bf16"][0] / r["mxfp8"][0], 3),
+               "verdict": "win" if r["mxfp8"][2] < r["bf16"][1] else
+               "loss" if r["mxfp8"][1] > r["bf16"][2] else "tie"}
+        for name, t in r.items():
+            row[name + "_us"] = round(t[0], 2)
+            row[name + "_us_min_max"] = [round(x, 2) for x in t[1:]]
+        print(json.dumps(row), flush=True)
+        if not sweep:
+            continue
+        rs = time_alternating({s: capture(fn(km, vm, s))[0]
+                               for s in (1, 2, 4, 8, 16)})
+        print(json.dumps({
+            "bench": "decode_attn_kv8_splits", "B": B, "H": H, "Hkv": Hkv,
+            "D": D, "S_max": S_max, "pos": p, "auto": auto,
+            "mxfp8_us_by_splits": {str(s): [round(x, 2) for x in t]
+                                   for s, t in rs.items()},
+        }), flush=True)
+
+
+def main_kv8():
+    # the G = 1 table (no rope)
+    run_kv8_shape(32, 16, 16, 64, 640, (512, 639), False, sweep=True)
+    run_kv8_shape(32, 8, 8, 128, 640, (639,), False, sweep=True)
+    run_kv8_shape(4, 16, 16, 64, 640, (639,), False, sweep=True)
+    run_kv8_shape(1, 16, 16, 64, 2048, (2047,), False, sweep=True)
+    # the GQA + RoPE table
+    run_kv8_shape(32, 32, 8, 64, 640, (512, 639), True, sweep=True)
+    run_kv8_shape(32, 32, 4, 64, 640, (639,), True, sweep=True)
+    run_kv8_shape(32, 16, 4, 128, 640, (639,), True, sweep=True)
+    run_kv8_shape(4, 32, 8, 64, 640, (639,), True, sweep=True)
+    run_kv8_shape(1, 32, 8, 64, 2048, (2047,), True, sweep=True)
+    run_kv8_shape(32, 16, 16, 64, 640, (639,), True)
+    run_kv8_shape(32, 32, 16, 64, 640, (639,), True)
+    run_kv8_shape(32, 16, 16, 128, 640, (639,), True)
+    run_kv8_shape(32, 16, 8, 128, 640, (639,), True)
+    run_kv8_shape(32, 32, 4, 128, 640, (639,), True, sweep=True)
+
+
 def main():
     assert torch.cuda.is_available(), "bench_decode_attn needs a GPU"
     which = sys.argv[1] if len(sys.argv) > 1 else "all"
@@ -315,6 +390,8 @@ def main():
         run_shape(1, 16, 64, 2048, (2047,), sweep=True)
     if which in ("all", "gqa"):
         main_gqa()
+    if which == "kv8":
+        main_kv8()
 
 
 if __name__ == "__main__":

@@ -17,7 +17,9 @@ cast, @ V. Without rope (GPT-2) the rope calls drop out.
 `python bench_prefill_attn.py calls` prints one JSON line per (shape, p0);
 `... whole` runs Generator over a 2048-token prompt of llama-1b-gqa in one
 chunk and in chunks of 512, composed and fused alternated. With no argument
-both run and the lines are also written to profiles/prefill_attention.json."""
+both run and the lines are also written to profiles/prefill_attention.json.
+`... kv8` compares the fused op on bf16 caches with the same op on MXFP8
+caches at the shapes of `calls` and writes profiles/prefill_attention_kv8.json."""
 import json
 import math
 import os
@@ -125,7 +127,37 @@ def run_shape(role, B, T, H, Hkv, D, p0s, theta=THETA):
         })
 
 
-def main_calls():
+def run_kv8_shape(role, B, T, H, Hkv, D, p0s, theta=THETA):
+    """The fused op on bf16 caches against the same op on MXFP8 caches
+    (mx.MXCache: the KV8 instantiations of both kernels), same shape and
+    p0. A win is the slowest MX window beating the fastest bf16 one."""
+    from tepdist_amd.ops import mx
+    for p0 in p0s:
+        kc, vc, qkv = make_case(B, T, H, Hkv, D, p0)
+        km, vm = ([mx.MXCache(w.codes.view(t.shape),
+                              w.scales.view(*t.shape[:3], D // 32))
+                   for t in cs
+                   for w in [mx.mx_quantize(t.reshape(-1, D), "mxfp8")]]
+                  for cs in (kc, vc))
+        r = bd.time_alternating({
+            "bf16": bd.capture(fused_fn(kc, vc, qkv, p0, theta))[0],
+            "mxfp8": bd.capture(fused_fn(km, vm, qkv, p0, theta))[0]})
+        row = {"bench": "prefill_attn_kv8", "role": role, "B": B, "T": T,
+               "H": H, "Hkv": Hkv, "G": H // Hkv, "D": D, "p0": p0,
+               "rope": theta is not None,
+               "blocks": B * Hkv * ((T * (H // Hkv) + 127) // 128),
+               "kv_bytes_bf16": 2 * B * Hkv * (p0 + T) * D * 2,
+               "kv_bytes_mxfp8": 2 * B * Hkv * (p0 + T) * (D + D // 32),
+               "speedup": round(r["bf16"][0] / r["mxfp8"][0], 3),
+               "verdict": "win" if r["mxfp8"][2] < r["bf16"][1] else
+               "loss" if r["mxfp8"][1] > r["bf16"][2] else "tie"}
+        for name, t in r.items():
+            row[name + "_us"] = round(t[0], 2)
+            row[name + "_us_min_max"] = [round(x, 2) for x in t[1:]]
+        emit(row)
+
+
+def main_calls(run_shape=run_shape):
     run_shape("llama-1b-gqa chunk", 4, 512, 32, 8, 64, (0, 512, 1536))
     run_shape("verify-shaped step", 32, 8, 32, 8, 64, (512,))
     run_shape("llama-1b", 4, 512, 16, 16, 128, (0, 1536))
@@ -177,6 +209,11 @@ def main():
         main_calls()
     if which in ("all", "whole"):
         main_whole()
+    if which == "kv8":
+        main_calls(run_kv8_shape)
+        with open(os.path.join(ROOT, "profiles",
+                               "prefill_attention_kv8.json"), "w") as f:
+            json.dump(ROWS, f, indent=1)
     if which == "all":
         with open(os.path.join(ROOT, "profiles", "prefill_attention.json"),
                   "w") as f:

@@ -89,7 +89,20 @@ sites the skinny MX plan covers run ops.mx_quantize_act(x, roundtrip=True)
 into a buffer allocated once, then ops.linear_decode_mx /
 ops.swiglu_linear_decode_mx as before: the same values, only the order of
 the fp32 sum differs. There is no "auto" rule yet (docs/KERNELS.md "MX
-weights x MXFP8 activations")."""
+weights x MXFP8 activations").
+
+KV cache format (kv_format=, or TEPDIST_KV_FORMAT): "bf16" (default) = every
+path above as it was. "mxfp8" = the caches are mx.MXCache (e4m3 codes and one
+e8m0 scale byte per 32 elements of a row, 51.6 % of the bf16 bytes): every
+K/V row is quantized by the rule of ops/mx.py as it is appended, and every
+attention reads the quantized rows, so prefill and decode serve one model, a
+different one from the bf16-cache model; nothing selects it automatically.
+Single-token steps run ops.decode_attention and passes over more than one
+token ops.prefill_attention (the first chunk included) on the MXCache,
+whatever decode_attn and prefill_attn say. Where the GPU kernels do not cover
+the model (head dim, group size, dtype) and on CPU, the same two ops run as
+the reference ops on the same MXCache; there is never a bf16 copy of the
+cache (docs/KERNELS.md "MXFP8 KV cache")."""
 
 from __future__ import annotations
 
@@ -115,7 +128,8 @@ class Generator:
                  prefill_attn: Optional[str] = None,
                  weight_format: Optional[str] = None,
                  mx_linear: Optional[str] = None,
-                 act_format: Optional[str] = None):
+                 act_format: Optional[str] = None,
+                 kv_format: Optional[str] = None):
         assert model.env.tp_size == 1, "generation engine: tp=1 layout"
         self.m = model
         self.cfg = model.cfg
@@ -170,6 +184,12 @@ class Generator:
                 f"at its default, got weight_format={weight_format!r}, "
                 f"mx_linear={mx_linear!r}")
         self.act_format = act_format
+        if kv_format is None:
+            kv_format = os.environ.get("TEPDIST_KV_FORMAT", "bf16")
+        if kv_format not in ("bf16", "mxfp8"):
+            raise ValueError(
+                f"kv_format must be 'bf16' or 'mxfp8', got {kv_format!r}")
+        self.kv_format = kv_format
         # id(parameter) -> its MXWeight; empty = serve the bf16 weights
         self.mxw = {}
         if weight_format != "bf16":
@@ -241,6 +261,30 @@ class Generator:
         N, K = mw.shape
         w = ops.mx_dequantize(mw, out=self._dq[:N * K].view(N, K))
         return w if dtype == w.dtype else w.to(dtype)
+
+    def new_caches(self, B: int, S_max: int, device, dtype):
+        """Per-layer K and V caches [B, Hkv, S_max, D] in self.kv_format."""
+        D = self.cfg.n_embd // self.cfg.n_head
+        n = self.cfg.n_layer
+        if self.kv_format == "mxfp8":
+            return tuple([mx.kv_cache(B, self.kv_heads, S_max, D, device)
+                          for _ in range(n)] for _ in range(2))
+        return tuple([torch.zeros(B, self.kv_heads, S_max, D, dtype=dtype,
+                                  device=device) for _ in range(n)]
+                     for _ in range(2))
+
+    def _kv8_ops(self, x, kc, H, Hkv, D):
+        """The module whose decode_attention / prefill_attention serve MXFP8
+        caches, or None for bf16 caches: the public ops (the HIP kernels) on
+        the GPU where they cover the model, the reference ops on the same
+        MXCache elsewhere and on CPU."""
+        if not isinstance(kc[0], mx.MXCache):
+            return None
+        if x.is_cuda:
+            from tepdist_amd.ops import hip
+            if not hip.prefill_why_not(x.dtype, H, Hkv, D):
+                return ops
+        return ref
 
     def _fused_decode(self, x, D, G: int = 1) -> bool:
         """Whether single-token steps on tensors like x run the fused
@@ -343,6 +387,11 @@ class Generator:
         scale = 1.0 / math.sqrt(D)
         fused = T == 1 and self._fused_decode(x, D)
         pf = T > 1 and self._fused_prefill(x, H, H, D)
+        att = self._kv8_ops(x, kc, H, H, D)
+        if att is not None:        # MXFP8 caches: always the two cache ops
+            fused, pf = T == 1, T > 1
+        else:
+            att = ops
         if fused or pf:
             pos_t = torch.full((1,), pos, device=x.device, dtype=torch.long)
         for li, blk in enumerate(self.m.blocks):
@@ -352,14 +401,14 @@ class Generator:
                 # one op: cache append at pos.. and attention over
                 # 0..pos + t, on views of the packed projection
                 q4 = qkv.view(B, T, 3, H, D)
-                a = ops.prefill_attention(q4[:, :, 0], kc[li], vc[li], pos_t,
+                a = att.prefill_attention(q4[:, :, 0], kc[li], vc[li], pos_t,
                                           k_new=q4[:, :, 1],
                                           v_new=q4[:, :, 2]).reshape(B, T, d)
             elif fused:
                 # one kernel: cache append at pos + attention over 0..pos,
                 # reading q/k/v as views of the packed projection
                 q3 = qkv.view(B, 3, H, D)
-                a = ops.decode_attention(q3[:, 0], kc[li], vc[li], pos_t,
+                a = att.decode_attention(q3[:, 0], kc[li], vc[li], pos_t,
                                          k_new=q3[:, 1],
                                          v_new=q3[:, 2]).reshape(B, 1, d)
             else:
@@ -483,6 +532,11 @@ class Generator:
         theta = cfg.rope_theta
         fused = T == 1 and self._fused_decode(x, D, G)
         pf = T > 1 and self._fused_prefill(x, H, Hkv, D)
+        att = self._kv8_ops(x, kc, H, Hkv, D)
+        if att is not None:        # MXFP8 caches: always the two cache ops
+            fused, pf = T == 1, T > 1
+        else:
+            att = ops
         prefill = T > 1 and pos == 0
         if fused or pf:
             pos_t = torch.full((1,), pos, device=x.device, dtype=torch.long)
@@ -497,12 +551,12 @@ class Generator:
             if pf:
                 # one op: rope of q and the chunk's K rows at pos + t, cache
                 # append, attention over 0..pos + t, K/V read at Hkv heads
-                a = ops.prefill_attention(q, kc[li], vc[li], pos_t, k_new=k,
+                a = att.prefill_attention(q, kc[li], vc[li], pos_t, k_new=k,
                                           v_new=v, rope_theta=theta)
             elif fused:
                 # one kernel: rope of q and the new K row at pos, cache
                 # append, attention over 0..pos, on views of the projection
-                a = ops.decode_attention(q[:, 0], kc[li], vc[li], pos_t,
+                a = att.decode_attention(q[:, 0], kc[li], vc[li], pos_t,
                                          k_new=k[:, 0], v_new=v[:, 0],
                                          rope_theta=theta)
             else:
@@ -555,6 +609,11 @@ class Generator:
         theta = cfg.rope_theta
         x = self._embed(tok, cur_t)
         fused = self._fused_decode(x, D, G)
+        att = self._kv8_ops(x, kc, H, Hkv, D)
+        if att is not None:
+            fused = True
+        else:
+            att = ops
         if not fused:
             dead = (kpos > cur_t)                   # [S_max] device bool
         for li, blk in enumerate(self.m.blocks):
@@ -562,7 +621,7 @@ class Generator:
             if fused:
                 # the kernel reads cur_t on the device: rotates by it,
                 # appends at it and attends rows 0..cur_t only
-                a = ops.decode_attention(q[:, 0], kc[li], vc[li], cur_t,
+                a = att.decode_attention(q[:, 0], kc[li], vc[li], cur_t,
                                          k_new=k[:, 0], v_new=v[:, 0],
                                          rope_theta=theta)
             else:
@@ -598,6 +657,11 @@ class Generator:
         x = ops.embedding(tok.reshape(-1), self.m.wte).reshape(B, 1, d) \
             + ops.embedding(cur_t, self.m.wpe)
         fused = self._fused_decode(x, D)
+        att = self._kv8_ops(x, kc, H, H, D)
+        if att is not None:
+            fused = True
+        else:
+            att = ops
         if not fused:
             mask = (kpos > cur_t)                   # [S_max] device bool
         for li, blk in enumerate(self.m.blocks):
@@ -607,7 +671,7 @@ class Generator:
                 # the kernel reads cur_t on the device: appends k/v at
                 # cur_t and attends rows 0..cur_t only (no S_max sweep)
                 q3 = qkv.view(B, 3, H, D)
-                a = ops.decode_attention(q3[:, 0], kc[li], vc[li], cur_t,
+                a = att.decode_attention(q3[:, 0], kc[li], vc[li], cur_t,
                                          k_new=q3[:, 1],
                                          v_new=q3[:, 2]).reshape(B, 1, d)
             else:
@@ -682,10 +746,7 @@ class Generator:
         S_max = min(self.max_seq, S0 + max_new_tokens)
         dev = next(self.m.parameters()).device
         dt = next(self.m.parameters()).dtype
-        kc = [torch.zeros(B, self.kv_heads, S_max, D, dtype=dt, device=dev)
-              for _ in range(cfg.n_layer)]
-        vc = [torch.zeros(B, self.kv_heads, S_max, D, dtype=dt, device=dev)
-              for _ in range(cfg.n_layer)]
+        kc, vc = self.new_caches(B, S_max, dev, dt)
         if sampler == "auto":
             sampler = "device" if ids.is_cuda and dt in (
                 torch.float32, torch.bfloat16) else "host"

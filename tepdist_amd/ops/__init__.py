@@ -32,7 +32,11 @@ from tepdist_amd.ops.interface import (  # noqa: F401
     swiglu,
 )
 
-from tepdist_amd.ops.mx import MXWeight, mx_quantize  # noqa: E402,F401
+from tepdist_amd.ops.mx import (  # noqa: E402,F401
+    MXCache,
+    MXWeight,
+    mx_quantize,
+)
 
 # torch.fx: leaf-wrap the public ops IN THIS NAMESPACE (clients call
 # ops.<name>), so generic capture (ir/capture.from_fx) records op nodes

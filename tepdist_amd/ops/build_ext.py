@@ -27,6 +27,7 @@ SOURCES = [
     "gemm256.hip",
     "attention.hip",
     "decode_attention.hip",
+    "decode_attention_mx.hip",
     "prefill_attention.hip",
     "skinny_gemm.hip",
     "skinny_mx_gemm.hip",
@@ -94,6 +95,7 @@ def _needs_build() -> bool:
                                           CSRC / "mx_gemm_plan.h",
                                           CSRC / "mx_gemm_a8_plan.h",
                                           CSRC / "mx_dequant.h",
+                                          CSRC / "mx_kv.h",
                                           CSRC / "gemm_tile.h",
                                           CSRC / "rope_common.h",
                                           Path(__file__)]

@@ -367,6 +367,54 @@ PYBIND11_MODULE(_tepdist_hip, m) {
     check_launch();
   });
 
+  m.def("decode_attention_mx", [](uintptr_t q, uintptr_t k_new,
+                                  uintptr_t v_new, uintptr_t k_codes,
+                                  uintptr_t v_codes, uintptr_t k_scales,
+                                  uintptr_t v_scales, uintptr_t pos,
+                                  int pos_stride, uintptr_t out, uintptr_t ws,
+                                  int B, int H, int Hkv, int S_max, int D,
+                                  float scale, int splits, bool rope,
+                                  float rope_theta, int64_t q_bs,
+                                  int64_t q_hs, int64_t n_bs, int64_t n_hs,
+                                  int64_t c_bs, int64_t c_hs, int64_t c_rs,
+                                  int64_t s_bs, int64_t s_hs, int64_t s_rs,
+                                  uintptr_t stream) {
+    decode_attention_mx(
+        reinterpret_cast<void*>(q), reinterpret_cast<void*>(k_new),
+        reinterpret_cast<void*>(v_new), reinterpret_cast<void*>(k_codes),
+        reinterpret_cast<void*>(v_codes), reinterpret_cast<void*>(k_scales),
+        reinterpret_cast<void*>(v_scales),
+        reinterpret_cast<const int64_t*>(pos), pos_stride,
+        reinterpret_cast<void*>(out), reinterpret_cast<float*>(ws), B, H,
+        Hkv, S_max, D, scale, splits, rope, rope_theta, q_bs, q_hs, n_bs,
+        n_hs, c_bs, c_hs, c_rs, s_bs, s_hs, s_rs, S(stream));
+    check_launch();
+  });
+
+  m.def("prefill_attention_mx", [](uintptr_t q, uintptr_t k_new,
+                                   uintptr_t v_new, uintptr_t k_codes,
+                                   uintptr_t v_codes, uintptr_t k_scales,
+                                   uintptr_t v_scales, uintptr_t pos,
+                                   int pos_stride, uintptr_t out, int B,
+                                   int T, int H, int Hkv, int S_max, int D,
+                                   float scale, bool rope, float rope_theta,
+                                   int64_t q_bs, int64_t q_ts, int64_t q_hs,
+                                   int64_t n_bs, int64_t n_ts, int64_t n_hs,
+                                   int64_t c_bs, int64_t c_hs, int64_t c_rs,
+                                   int64_t s_bs, int64_t s_hs, int64_t s_rs,
+                                   uintptr_t stream) {
+    prefill_attention_mx(
+        reinterpret_cast<void*>(q), reinterpret_cast<void*>(k_new),
+        reinterpret_cast<void*>(v_new), reinterpret_cast<void*>(k_codes),
+        reinterpret_cast<void*>(v_codes), reinterpret_cast<void*>(k_scales),
+        reinterpret_cast<void*>(v_scales),
+        reinterpret_cast<const int64_t*>(pos), pos_stride,
+        reinterpret_cast<void*>(out), B, T, H, Hkv, S_max, D, scale, rope,
+        rope_theta, q_bs, q_ts, q_hs, n_bs, n_ts, n_hs, c_bs, c_hs, c_rs,
+        s_bs, s_hs, s_rs, S(stream));
+    check_launch();
+  });
+
   m.def("sample_logits", [](uintptr_t logits, bool logits_bf16,
                             int64_t row_stride, int B, int vocab,
                             float temperature, int top_k, float top_p,

@@ -196,6 +196,24 @@ void decode_attention_bf16(const void* q, const void* k_new,
                            int64_t c_bs, int64_t c_hs, int64_t c_rs,
                            hipStream_t stream);
 
+// The same op over an MXFP8 cache (decode_attention_mx.hip; ops/mx.py
+// MXCache): k/v_codes [B,Hkv,S_max,D] e4m3 bytes sharing byte strides (c_bs,
+// c_hs, c_rs), 8-byte-aligned rows; k/v_scales [B,Hkv,S_max,D/32] e8m0 bytes
+// sharing (s_bs, s_hs, s_rs), any alignment. q, k_new, v_new, out, pos, ws,
+// splits and the position semantics as above. The new row is rotated in fp32
+// (rope), rounded once to bf16 and quantized by mx_quantize's rule (the
+// integer rule of mx_gemm_a8_plan.h); the quantized row is what is attended
+// to and what cache row p receives, codes and scale bytes.
+void decode_attention_mx(const void* q, const void* k_new, const void* v_new,
+                         void* k_codes, void* v_codes, void* k_scales,
+                         void* v_scales, const int64_t* pos, int pos_stride,
+                         void* out, float* ws, int B, int H, int Hkv,
+                         int S_max, int D, float scale, int splits, bool rope,
+                         float rope_theta, int64_t q_bs, int64_t q_hs,
+                         int64_t n_bs, int64_t n_hs, int64_t c_bs,
+                         int64_t c_hs, int64_t c_rs, int64_t s_bs,
+                         int64_t s_hs, int64_t s_rs, hipStream_t stream);
+
 // --- Prefill attention over a KV cache (prefill_attention.hip) -------------
 // A chunk of T query tokens per batch row against the cache. q: [B,T,H,D]
 // bf16 (q_bs, q_ts, q_hs element strides, D contiguous); k_new/v_new:
@@ -217,6 +235,22 @@ void prefill_attention_bf16(const void* q, const void* k_new,
                             int64_t n_bs, int64_t n_ts, int64_t n_hs,
                             int64_t c_bs, int64_t c_hs, int64_t c_rs,
                             hipStream_t stream);
+
+// The same op over an MXFP8 cache (ops/mx.py MXCache; the KV8 instantiations
+// of the two kernels): codes and scales as in decode_attention_mx, byte
+// strides (c_*) and (s_*). The chunk's rows are rotated and rounded as above,
+// then quantized by mx_quantize's rule and stored as codes and scale bytes;
+// the attention stages dequantized (exact) bf16 tiles.
+void prefill_attention_mx(const void* q, const void* k_new, const void* v_new,
+                          void* k_codes, void* v_codes, void* k_scales,
+                          void* v_scales, const int64_t* pos, int pos_stride,
+                          void* out, int B, int T, int H, int Hkv, int S_max,
+                          int D, float scale, bool rope, float rope_theta,
+                          int64_t q_bs, int64_t q_ts, int64_t q_hs,
+                          int64_t n_bs, int64_t n_ts, int64_t n_hs,
+                          int64_t c_bs, int64_t c_hs, int64_t c_rs,
+                          int64_t s_bs, int64_t s_hs, int64_t s_rs,
+                          hipStream_t stream);
 
 // --- Token sampling (sampling.hip) -----------------------------------------
 // out[b] (int64 [B]) := one token of row b of logits [B, >= vocab] (fp32, or

@@ -44,6 +44,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "lds_frag.h"
+#include "mx_kv.h"
 #include "rope_common.h"
 
 namespace tepdist {
@@ -76,7 +77,14 @@ DEV_INLINE int clamp_p0(const int64_t* pos, int b, int pos_stride, int S_max,
 // append (+ rotate)
 // ---------------------------------------------------------------------------
 
-template <int D, bool ROPE>
+// KV8: the caches are MXFP8 (ops/mx.py MXCache). k_cache / v_cache then point
+// at the e4m3 codes with (c_bs, c_hs, c_rs) in bytes, k_sc / v_sc at the e8m0
+// scale bytes with (s_bs, s_hs, s_rs); the row is rotated and rounded as
+// below, then quantized in registers by mx_quantize's rule (mxkv_quant8: the
+// four lanes of a quad hold one block; LPR is a multiple of 4, so a quad is
+// wholly inside or outside the problem) and stored as 8 code bytes per lane
+// and one scale byte per quad.
+template <int D, bool ROPE, bool KV8 = false>
 __launch_bounds__(NT) __global__
 void prefill_append_kernel(const bf16_t* __restrict__ k_new,
                            const bf16_t* __restrict__ v_new,
@@ -86,7 +94,11 @@ void prefill_append_kernel(const bf16_t* __restrict__ k_new,
                            int B, int T, int Hkv, int S_max,
                            float neg2_over_d, float ltheta, int64_t n_bs,
                            int64_t n_ts, int64_t n_hs, int64_t c_bs,
-                           int64_t c_hs, int64_t c_rs) {
+                           int64_t c_hs, int64_t c_rs,
+                           uint8_t* __restrict__ k_sc = nullptr,
+                           uint8_t* __restrict__ v_sc = nullptr,
+                           int64_t s_bs = 0, int64_t s_hs = 0,
+                           int64_t s_rs = 0) {
   constexpr int LPR = D / 8;  // lanes per row
   const int64_t idx = (int64_t)blockIdx.x * NT + threadIdx.x;
   if (idx >= (int64_t)B * T * Hkv * LPR) return;
@@ -114,8 +126,26 @@ void prefill_append_kernel(const bf16_t* __restrict__ k_new,
       k8[e] = f2bf(col < D / 2 ? x * cs - y * sn : x * cs + y * sn);
     }
   }
-  *reinterpret_cast<bf16x8*>(k_cache + dst) = k8;
-  *reinterpret_cast<bf16x8*>(v_cache + dst) = v8;
+  if constexpr (KV8) {
+    const u32x4 kw = __builtin_bit_cast(u32x4, k8);
+    const u32x4 vw = __builtin_bit_cast(u32x4, v8);
+    unsigned kq0, kq1, kqb, vq0, vq1, vqb;
+    mxkv_quant8(kw[0], kw[1], kw[2], kw[3], kq0, kq1, kqb);
+    mxkv_quant8(vw[0], vw[1], vw[2], vw[3], vq0, vq1, vqb);
+    *reinterpret_cast<uint2*>(reinterpret_cast<uint8_t*>(k_cache) + dst) =
+        make_uint2(kq0, kq1);
+    *reinterpret_cast<uint2*>(reinterpret_cast<uint8_t*>(v_cache) + dst) =
+        make_uint2(vq0, vq1);
+    if ((threadIdx.x & 3) == 0) {
+      const int64_t sd =
+          b * s_bs + hk * s_hs + (int64_t)p * s_rs + (col >> 5);
+      k_sc[sd] = (uint8_t)kqb;
+      v_sc[sd] = (uint8_t)vqb;
+    }
+  } else {
+    *reinterpret_cast<bf16x8*>(k_cache + dst) = k8;
+    *reinterpret_cast<bf16x8*>(v_cache + dst) = v8;
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -124,7 +154,11 @@ void prefill_append_kernel(const bf16_t* __restrict__ k_new,
 
 // lg = log2(G). Row r of the (b, kv head) problem is token r >> lg, group
 // member r & (G - 1), i.e. query head hk * G + (r & (G - 1)).
-template <int D, bool ROPE>
+// KV8: Kc / Vc point at e4m3 codes with byte strides, Ks / Vs at the scale
+// bytes (see prefill_append_kernel). Only the staging differs: stage_load
+// fetches 8 code bytes and the block's scale byte per slot, stage_write
+// dequantizes them (dq_fp8, exact) into the same swizzled bf16 images.
+template <int D, bool ROPE, bool KV8 = false>
 __launch_bounds__(NT) __global__
 void prefill_attn_kernel(const bf16_t* __restrict__ Q,
                          const bf16_t* __restrict__ Kc,
@@ -134,7 +168,11 @@ void prefill_attn_kernel(const bf16_t* __restrict__ Q,
                          int S_max, float scale, float neg2_over_d,
                          float ltheta, int64_t q_bs, int64_t q_ts,
                          int64_t q_hs, int64_t c_bs, int64_t c_hs,
-                         int64_t c_rs) {
+                         int64_t c_rs,
+                         const uint8_t* __restrict__ Ks = nullptr,
+                         const uint8_t* __restrict__ Vs = nullptr,
+                         int64_t s_bs = 0, int64_t s_hs = 0,
+                         int64_t s_rs = 0) {
   constexpr int DK = D / 32;  // k-chunks per d-contraction fragment
   constexpr int DF = D / 16;  // d row fragments of O^T
   const int G = 1 << lg;
@@ -156,8 +194,13 @@ void prefill_attn_kernel(const bf16_t* __restrict__ Q,
   const int tw_lo = wr0 >> lg;
   const int tw_hi = min(T - 1, (wr0 + 31) >> lg);
 
-  const bf16_t* kp = Kc + b * c_bs + hk * c_hs;
-  const bf16_t* vp = Vc + b * c_bs + hk * c_hs;
+  // this (b, kv head)'s planes: bf16 rows, or (KV8, byte strides) codes
+  const bf16_t* kp = KV8 ? nullptr : Kc + b * c_bs + hk * c_hs;
+  const bf16_t* vp = KV8 ? nullptr : Vc + b * c_bs + hk * c_hs;
+  const uint8_t* kq = reinterpret_cast<const uint8_t*>(Kc) +
+                      (KV8 ? b * c_bs + hk * c_hs : 0);
+  const uint8_t* vq = reinterpret_cast<const uint8_t*>(Vc) +
+                      (KV8 ? b * c_bs + hk * c_hs : 0);
 
   __shared__ __attribute__((aligned(16))) bf16_t smem[2 * 2 * KB * D];
   constexpr int BUFSZ = 2 * KB * D;  // K and V, both natural [KB][D]
@@ -206,6 +249,10 @@ void prefill_attn_kernel(const bf16_t* __restrict__ Q,
   // per thread. Rows at or past kv_end re-load row kv_end - 1.
   constexpr int KUN = KB * D / 8 / NT;
   bf16x8 krg[KUN], vrg[KUN];
+  // KV8: 8 codes and the block's scale byte per slot; a clamped row re-loads
+  // the last visible row's codes and scales
+  uint2 kcd[KUN], vcd[KUN];
+  unsigned ksc[KUN], vsc[KUN];
   auto stage_load = [&](int kv0) {
 #pragma unroll
     for (int u = 0; u < KUN; ++u) {
@@ -213,8 +260,16 @@ void prefill_attn_kernel(const bf16_t* __restrict__ Q,
       const int c = (idx % (D / 8)) * 8;
       int j = kv0 + idx / (D / 8);
       j = j < kv_end ? j : kv_end - 1;
-      krg[u] = *reinterpret_cast<const bf16x8*>(kp + (int64_t)j * c_rs + c);
-      vrg[u] = *reinterpret_cast<const bf16x8*>(vp + (int64_t)j * c_rs + c);
+      if constexpr (KV8) {
+        const int64_t so = b * s_bs + hk * s_hs + (int64_t)j * s_rs + (c >> 5);
+        kcd[u] = *reinterpret_cast<const uint2*>(kq + (int64_t)j * c_rs + c);
+        vcd[u] = *reinterpret_cast<const uint2*>(vq + (int64_t)j * c_rs + c);
+        ksc[u] = Ks[so];
+        vsc[u] = Vs[so];
+      } else {
+        krg[u] = *reinterpret_cast<const bf16x8*>(kp + (int64_t)j * c_rs + c);
+        vrg[u] = *reinterpret_cast<const bf16x8*>(vp + (int64_t)j * c_rs + c);
+      }
     }
   };
   auto stage_write = [&](int buf) {
@@ -225,6 +280,10 @@ void prefill_attn_kernel(const bf16_t* __restrict__ Q,
       const int idx = threadIdx.x + u * NT;
       const int row = idx / (D / 8);
       const int c = (idx % (D / 8)) * 8;
+      if constexpr (KV8) {
+        krg[u] = dq_fp8(kcd[u].x, kcd[u].y, mx_scale(ksc[u]));
+        vrg[u] = dq_fp8(vcd[u].x, vcd[u].y, mx_scale(vsc[u]));
+      }
       *reinterpret_cast<bf16x8*>(sK + loff<D>(row, c)) = krg[u];
       *reinterpret_cast<bf16x8*>(sV + loff<D>(row, c)) = vrg[u];
     }
@@ -347,17 +406,10 @@ bool aligned16(const void* p) {
   return (reinterpret_cast<uintptr_t>(p) & 15) == 0;
 }
 
-}  // namespace
-
-void prefill_attention_bf16(const void* q, const void* k_new,
-                            const void* v_new, void* k_cache, void* v_cache,
-                            const int64_t* pos, int pos_stride, void* out,
-                            int B, int T, int H, int Hkv, int S_max, int D,
-                            float scale, bool rope, float rope_theta,
-                            int64_t q_bs, int64_t q_ts, int64_t q_hs,
-                            int64_t n_bs, int64_t n_ts, int64_t n_hs,
-                            int64_t c_bs, int64_t c_hs, int64_t c_rs,
-                            hipStream_t stream) {
+// checks shared by the bf16 and the MXFP8 cache entry points
+int check_problem(int B, int T, int H, int Hkv, int S_max, int D, float scale,
+                  bool rope, float rope_theta, int pos_stride,
+                  const void* k_new, const void* v_new) {
   if (D != 64 && D != 128)
     throw std::runtime_error("prefill_attention: head dim must be 64 or 128");
   if (B < 1 || B > 65535 || Hkv < 1 || Hkv > 65535 || T < 1 || S_max < 1)
@@ -382,6 +434,90 @@ void prefill_attention_bf16(const void* q, const void* k_new,
     throw std::runtime_error("prefill_attention: pos_stride must be 0 or 1");
   if ((k_new == nullptr) != (v_new == nullptr))
     throw std::runtime_error("prefill_attention: k_new/v_new go together");
+  return G;
+}
+
+}  // namespace
+
+void prefill_attention_mx(const void* q, const void* k_new, const void* v_new,
+                          void* k_codes, void* v_codes, void* k_scales,
+                          void* v_scales, const int64_t* pos, int pos_stride,
+                          void* out, int B, int T, int H, int Hkv, int S_max,
+                          int D, float scale, bool rope, float rope_theta,
+                          int64_t q_bs, int64_t q_ts, int64_t q_hs,
+                          int64_t n_bs, int64_t n_ts, int64_t n_hs,
+                          int64_t c_bs, int64_t c_hs, int64_t c_rs,
+                          int64_t s_bs, int64_t s_hs, int64_t s_rs,
+                          hipStream_t stream) {
+  const int G = check_problem(B, T, H, Hkv, S_max, D, scale, rope, rope_theta,
+                              pos_stride, k_new, v_new);
+  if (!q || !k_codes || !v_codes || !k_scales || !v_scales || !pos || !out)
+    throw std::runtime_error("prefill_attention: null operand");
+  if (!aligned16(q) || !aligned16(k_new) || !aligned16(v_new) ||
+      !aligned16(out) || ((q_bs | q_ts | q_hs) & 7) ||
+      (k_new && ((n_bs | n_ts | n_hs) & 7)))
+    throw std::runtime_error(
+        "prefill_attention: q, k_new, v_new and out must be 16-byte aligned "
+        "with strides that are multiples of 8 elements");
+  if ((reinterpret_cast<uintptr_t>(k_codes) & 7) ||
+      (reinterpret_cast<uintptr_t>(v_codes) & 7) ||
+      ((c_bs | c_hs | c_rs) & 7))
+    throw std::runtime_error(
+        "prefill_attention: MX cache code rows must be 8-byte aligned (base "
+        "and strides multiples of 8 bytes)");
+  if (c_rs < D || s_rs < D / 32)
+    throw std::runtime_error("prefill_attention: MX cache row stride below "
+                             "D codes or D / 32 scale bytes");
+
+  const float ltheta = rope ? logf(rope_theta) : 0.f;
+  const float neg2 = -2.0f / D;
+  // the kernels' cache pointers are typed for the bf16 case; KV8 reads them
+  // as bytes
+  bf16_t* kcp = static_cast<bf16_t*>(k_codes);
+  bf16_t* vcp = static_cast<bf16_t*>(v_codes);
+  uint8_t* ksp = static_cast<uint8_t*>(k_scales);
+  uint8_t* vsp = static_cast<uint8_t*>(v_scales);
+  int lg = 0;
+  while ((1 << lg) < G) ++lg;
+
+#define PA8_LAUNCH(DD, RR)                                                   \
+  do {                                                                       \
+    if (k_new) {                                                             \
+      const int64_t n = (int64_t)B * T * Hkv * (DD / 8);                     \
+      hipLaunchKernelGGL((prefill_append_kernel<DD, RR, true>),              \
+                         dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0,   \
+                         stream, static_cast<const bf16_t*>(k_new),          \
+                         static_cast<const bf16_t*>(v_new), kcp, vcp, pos,   \
+                         pos_stride, B, T, Hkv, S_max, neg2, ltheta, n_bs,   \
+                         n_ts, n_hs, c_bs, c_hs, c_rs, ksp, vsp, s_bs, s_hs, \
+                         s_rs);                                              \
+    }                                                                        \
+    hipLaunchKernelGGL((prefill_attn_kernel<DD, RR, true>),                  \
+                       dim3((T * G + QB - 1) / QB, Hkv, B), dim3(NT), 0,     \
+                       stream, static_cast<const bf16_t*>(q), kcp, vcp, pos, \
+                       pos_stride, static_cast<bf16_t*>(out), T, H, lg,      \
+                       S_max, scale, neg2, ltheta, q_bs, q_ts, q_hs, c_bs,   \
+                       c_hs, c_rs, ksp, vsp, s_bs, s_hs, s_rs);              \
+  } while (0)
+  if (D == 64) {
+    if (rope) PA8_LAUNCH(64, true); else PA8_LAUNCH(64, false);
+  } else {
+    if (rope) PA8_LAUNCH(128, true); else PA8_LAUNCH(128, false);
+  }
+#undef PA8_LAUNCH
+}
+
+void prefill_attention_bf16(const void* q, const void* k_new,
+                            const void* v_new, void* k_cache, void* v_cache,
+                            const int64_t* pos, int pos_stride, void* out,
+                            int B, int T, int H, int Hkv, int S_max, int D,
+                            float scale, bool rope, float rope_theta,
+                            int64_t q_bs, int64_t q_ts, int64_t q_hs,
+                            int64_t n_bs, int64_t n_ts, int64_t n_hs,
+                            int64_t c_bs, int64_t c_hs, int64_t c_rs,
+                            hipStream_t stream) {
+  const int G = check_problem(B, T, H, Hkv, S_max, D, scale, rope, rope_theta,
+                              pos_stride, k_new, v_new);
   if (!q || !k_cache || !v_cache || !pos || !out)
     throw std::runtime_error("prefill_attention: null operand");
   // 16-byte vector access on every row: bases and strides in 8-element units
@@ -412,13 +548,16 @@ void prefill_attention_bf16(const void* q, const void* k_new,
                          stream, static_cast<const bf16_t*>(k_new),          \
                          static_cast<const bf16_t*>(v_new), kcp, vcp, pos,   \
                          pos_stride, B, T, Hkv, S_max, neg2, ltheta, n_bs,   \
-                         n_ts, n_hs, c_bs, c_hs, c_rs);                      \
+                         n_ts, n_hs, c_bs, c_hs, c_rs, nullptr, nullptr,     \
+                         (int64_t)0, (int64_t)0, (int64_t)0);                \
     }                                                                        \
     hipLaunchKernelGGL((prefill_attn_kernel<DD, RR>),                        \
                        dim3((T * G + QB - 1) / QB, Hkv, B), dim3(NT), 0,     \
                        stream, qp, kcp, vcp, pos, pos_stride,                \
                        static_cast<bf16_t*>(out), T, H, lg, S_max, scale,    \
-                       neg2, ltheta, q_bs, q_ts, q_hs, c_bs, c_hs, c_rs);    \
+                       neg2, ltheta, q_bs, q_ts, q_hs, c_bs, c_hs, c_rs,     \
+                       nullptr, nullptr, (int64_t)0, (int64_t)0,             \
+                       (int64_t)0);                                          \
   } while (0)
   if (D == 64) {
     if (rope) PA_LAUNCH(64, true); else PA_LAUNCH(64, false);

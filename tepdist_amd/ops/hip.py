@@ -14,6 +14,8 @@ from typing import Optional, Tuple
 
 import torch
 
+from tepdist_amd.ops import mx
+
 try:
     from tepdist_amd.ops import _tepdist_hip as ext
 except ImportError as e:  # pragma: no cover
@@ -1174,6 +1176,126 @@ def decode_splits(bh: int, s_max: int, group: int = 1) -> int:
     return s
 
 
+def _mx_kv(name: str, k_cache, v_cache) -> bool:
+    """Whether the caches are a pair of mx.MXCache; a mixed pair raises."""
+    mk, mv = isinstance(k_cache, mx.MXCache), isinstance(v_cache, mx.MXCache)
+    if mk != mv:
+        raise ValueError(f"{name}: k_cache and v_cache must both be MXCache "
+                         "or both be bf16 tensors")
+    return mk
+
+
+def _mx_kv_operands(name, q, lead, H, D, k_cache, v_cache, positions, k_new,
+                    v_new, rope_theta):
+    """The checks the two MXFP8-cache ops share. lead: q's leading dims, (B,)
+    or (B, T). Returns (Hkv, S_max, new-row strides, pos, pos_stride)."""
+    B = lead[0]
+    _, Hkv, S_max, Dc = mx.check_cache(k_cache)     # fmt, D % 32, shapes
+    if mx.check_cache(v_cache) != tuple(k_cache.shape) or \
+            (B, Dc) != (k_cache.shape[0], D) or \
+            v_cache.codes.stride() != k_cache.codes.stride() or \
+            v_cache.scales.stride() != k_cache.scales.stride():
+        raise ValueError(f"{name}: k_cache/v_cache must be MXCaches "
+                         "[B,Hkv,S_max,D] with equal strides")
+    why = prefill_why_not(q.dtype, H, Hkv, D)    # the same coverage
+    if why:
+        raise ValueError(f"{name}: " + why)
+    codes, scales = k_cache.codes, k_cache.scales
+    if any(t is not None and t.device != q.device for t in (
+            codes, scales, v_cache.codes, v_cache.scales, k_new, v_new)):
+        raise ValueError(f"{name}: caches and new rows must be on q's "
+                         f"device, {q.device}")
+    if q.stride(-1) != 1 or codes.stride(3) != 1 or scales.stride(3) != 1:
+        raise ValueError(f"{name}: D must be contiguous")
+    if any(st % 8 for st in codes.stride()[:3]) or \
+            k_cache.codes.data_ptr() % 8 or v_cache.codes.data_ptr() % 8:
+        raise ValueError(f"{name}: MXCache code rows must be 8-byte aligned")
+    if (k_new is None) != (v_new is None):
+        raise ValueError(f"{name}: k_new and v_new go together")
+    if rope_theta is not None and not rope_theta > 0:
+        raise ValueError(f"{name}: rope_theta must be positive")
+    n_st = (0,) * (len(lead) + 1)
+    if k_new is not None:
+        if k_new.dtype != BF16 or v_new.dtype != BF16 or \
+                tuple(k_new.shape) != (*lead, Hkv, D) or \
+                v_new.shape != k_new.shape or \
+                k_new.stride() != v_new.stride() or k_new.stride(-1) != 1:
+            raise ValueError(f"{name}: k_new/v_new must be bf16 "
+                             f"{[*lead, Hkv, D]} with equal strides, D "
+                             "contiguous")
+        n_st = k_new.stride()[:-1]
+    pos = positions.reshape(-1)
+    if pos.dtype != torch.int64 or pos.device != q.device or \
+            pos.numel() not in (1, B):
+        raise ValueError(f"{name}: positions must be a device int64 tensor "
+                         "with 1 or B elements")
+    return Hkv, S_max, n_st, pos.contiguous(), \
+        1 if (pos.numel() == B and B > 1) else 0
+
+
+def _decode_attention_mx(q, k_cache, v_cache, positions, k_new, v_new, scale,
+                         splits, rope_theta):
+    if q.dim() != 3:
+        raise ValueError("decode_attention: q [B,H,D]")
+    B, H, D = q.shape
+    Hkv, S_max, n_st, pos, pos_stride = _mx_kv_operands(
+        "decode_attention", q, (B,), H, D, k_cache, v_cache, positions,
+        k_new, v_new, rope_theta)
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    if splits is None:
+        splits = decode_splits(B * Hkv, S_max, H // Hkv)
+    out = torch.empty(B, H, D, dtype=BF16, device=q.device)
+    ws = torch.empty(B * H * splits * (D + 2), dtype=torch.float32,
+                     device=q.device) if splits > 1 else None
+    try:
+        ext.decode_attention_mx(
+            q.data_ptr(), _p(k_new), _p(v_new), k_cache.codes.data_ptr(),
+            v_cache.codes.data_ptr(), k_cache.scales.data_ptr(),
+            v_cache.scales.data_ptr(), pos.data_ptr(), pos_stride,
+            out.data_ptr(), _p(ws), B, H, Hkv, S_max, D, scale, splits,
+            rope_theta is not None, float(rope_theta or 0.0), q.stride(0),
+            q.stride(1), *n_st, *k_cache.codes.stride()[:3],
+            *k_cache.scales.stride()[:3], _stream())
+    except RuntimeError as e:      # alignment / stride / size refusals
+        if "decode_attention:" not in str(e):
+            raise
+        raise ValueError(str(e)) from None
+    return out
+
+
+def _prefill_attention_mx(q, k_cache, v_cache, positions, k_new, v_new,
+                          scale, rope_theta):
+    if q.dim() != 4:
+        raise ValueError("prefill_attention: q [B,T,H,D]")
+    B, T, H, D = q.shape
+    Hkv, S_max, n_st, pos, pos_stride = _mx_kv_operands(
+        "prefill_attention", q, (B, T), H, D, k_cache, v_cache, positions,
+        k_new, v_new, rope_theta)
+    if T < 1 or T > S_max:
+        raise ValueError(f"prefill_attention: chunk of {T} tokens does not "
+                         f"fit a cache of {S_max} rows")
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    if not scale > 0:
+        raise ValueError("prefill_attention: scale must be positive")
+    out = torch.empty(B, T, H, D, dtype=BF16, device=q.device)
+    try:
+        ext.prefill_attention_mx(
+            q.data_ptr(), _p(k_new), _p(v_new), k_cache.codes.data_ptr(),
+            v_cache.codes.data_ptr(), k_cache.scales.data_ptr(),
+            v_cache.scales.data_ptr(), pos.data_ptr(), pos_stride,
+            out.data_ptr(), B, T, H, Hkv, S_max, D, scale,
+            rope_theta is not None, float(rope_theta or 0.0),
+            *q.stride()[:3], *n_st, *k_cache.codes.stride()[:3],
+            *k_cache.scales.stride()[:3], _stream())
+    except RuntimeError as e:      # alignment / stride / size refusals
+        if "prefill_attention:" not in str(e):
+            raise
+        raise ValueError(str(e)) from None
+    return out
+
+
 def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
                      v_cache: torch.Tensor, positions: torch.Tensor,
                      k_new: Optional[torch.Tensor] = None,
@@ -1187,7 +1309,11 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
     queries (caches and new rows with Hkv heads, H / Hkv in {1, 2, 4, 8})
     and the in-kernel rotation of q and k_new when rope_theta is given.
     Strided [B, H, D] views (e.g. of the packed qkv projection) and cache
-    slices are consumed without a copy."""
+    slices are consumed without a copy. A pair of mx.MXCache runs
+    decode_attention_mx.hip: the new row is quantized on the way in."""
+    if _mx_kv("decode_attention", k_cache, v_cache):
+        return _decode_attention_mx(q, k_cache, v_cache, positions, k_new,
+                                    v_new, scale, splits, rope_theta)
     if q.dim() != 3 or k_cache.dim() != 4:
         raise ValueError("decode_attention: q [B,H,D], caches "
                          "[B,Hkv,S_max,D]")
@@ -1279,7 +1405,12 @@ def prefill_attention(q: torch.Tensor, k_cache: torch.Tensor,
     (prefill_attention.hip). Same semantics as reference.prefill_attention,
     including the in-place cache write of (k_new, v_new) at the device-side
     position and the in-kernel rotation of q and k_new. Strided views with
-    D contiguous (e.g. of the packed qkv projection) are read in place."""
+    D contiguous (e.g. of the packed qkv projection) are read in place. A
+    pair of mx.MXCache runs the kernels' KV8 instantiations: the chunk's rows
+    are quantized on the way in."""
+    if _mx_kv("prefill_attention", k_cache, v_cache):
+        return _prefill_attention_mx(q, k_cache, v_cache, positions, k_new,
+                                     v_new, scale, rope_theta)
     if q.dim() != 4 or k_cache.dim() != 4:
         raise ValueError("prefill_attention: q [B,T,H,D], caches "
                          "[B,Hkv,S_max,D]")

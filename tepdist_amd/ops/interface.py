@@ -284,8 +284,21 @@ def decode_attention(q, k_cache, v_cache, positions, k_new=None, v_new=None,
     rotated (rotate-half, as ops.rope) by the clamped position first: q in
     fp32 without rounding, k_new rounded once to the cache dtype, so the
     cache holds rotated rows. `splits` (GPU only) pins the KV split count;
-    None = host heuristic."""
-    for t in (q, k_cache, v_cache, k_new, v_new):
+    None = host heuristic.
+
+    MXFP8 cache: k_cache and v_cache may both be an mx.MXCache (e4m3 codes
+    [B, Hkv, S_max, D] and one e8m0 scale byte per 32 d of a row); q, k_new
+    and v_new stay bf16. The op is then the one above on
+    mx.cache_dequantize(cache), except that the appended row is quantized on
+    the way in: k_new is rotated in fp32, rounded once to bf16 and quantized
+    by the rule of mx.mx_quantize(row, "mxfp8"), v_new is quantized as it
+    is; codes and scale bytes are written into row positions[b] and the
+    dequantized row is what is attended to, so the result equals
+    write-then-attend. On the GPU: D in {64, 128}, H / Hkv in {1, 2, 4, 8},
+    8-byte-aligned code rows; anything else, a mixed pair of cache types
+    included, raises ValueError."""
+    for t in (q, k_new, v_new) + tuple(
+            c for c in (k_cache, v_cache) if isinstance(c, torch.Tensor)):
         assert t is None or not t.requires_grad, \
             "decode_attention has no backward"
     be = _backend(q)
@@ -311,8 +324,16 @@ def prefill_attention(q, k_cache, v_cache, positions, k_new=None, v_new=None,
     p0 + t, each rounded once to the tensors' dtype, so the cache holds
     rotated rows. Rows above p0 + T - 1 have no influence. Returns
     [B, T, H, D], contiguous. On the GPU: bf16, D in {64, 128},
-    H / Hkv in {1, 2, 4, 8}; anything else raises ValueError."""
-    for t in (q, k_cache, v_cache, k_new, v_new):
+    H / Hkv in {1, 2, 4, 8}; anything else raises ValueError.
+
+    MXFP8 cache: k_cache and v_cache may both be an mx.MXCache, as for
+    decode_attention. The op is then the one above on
+    mx.cache_dequantize(cache), with the chunk's rows quantized on the way
+    in: K rotated in fp32 and rounded once to bf16, then K and V quantized by
+    the rule of mx.mx_quantize(row, "mxfp8") and written as codes and scale
+    bytes into rows p0 + t."""
+    for t in (q, k_new, v_new) + tuple(
+            c for c in (k_cache, v_cache) if isinstance(c, torch.Tensor)):
         assert t is None or not t.requires_grad, \
             "prefill_attention has no backward"
     return _backend(q).prefill_attention(q, k_cache, v_cache, positions,

@@ -153,3 +153,88 @@ def dequantize_ref(mw: MXWeight) -> torch.Tensor:
     e = mw.scales.to(torch.int32) - 127
     return torch.ldexp(v.reshape(N, K // BLOCK, BLOCK),
                        e[..., None]).reshape(N, K).to(torch.bfloat16)
+
+
+# --------------------------------------------------------------------------
+# MXFP8 KV cache
+# --------------------------------------------------------------------------
+
+@dataclass
+class MXCache:
+    """A K or V cache held as MXFP8: codes uint8 [B, Hkv, S_max, D] (e4m3,
+    `fn` encoding) and scales uint8 [B, Hkv, S_max, D / 32] (e8m0), fmt
+    "mxfp8" only. Every (b, h) plane is an MXWeight [S_max, D] in the layout
+    above: a block is 32 consecutive d of one row, scale bytes lie in
+    [10, 246] and the NaN codes are never written. Views are allowed (a batch
+    slice, an S_max slice of a larger buffer) as long as D is contiguous and
+    code rows are 8-byte aligned; codes and scales carry their own strides."""
+    codes: torch.Tensor
+    scales: torch.Tensor
+    fmt: str = "mxfp8"
+
+    @property
+    def shape(self):
+        return tuple(self.codes.shape)
+
+    def to(self, device) -> "MXCache":
+        return MXCache(self.codes.to(device), self.scales.to(device),
+                       self.fmt)
+
+    def clone(self) -> "MXCache":
+        return MXCache(self.codes.clone(), self.scales.clone(), self.fmt)
+
+    @property
+    def nbytes(self) -> int:
+        return self.codes.numel() + self.scales.numel()
+
+
+def kv_cache(B: int, Hkv: int, S_max: int, D: int, device=None) -> MXCache:
+    """A zero-filled MXFP8 cache: every code 0, every scale byte 127."""
+    if D % BLOCK:
+        raise ValueError(f"kv_cache: head dim {D} is no multiple of {BLOCK}")
+    return MXCache(
+        torch.zeros(B, Hkv, S_max, D, dtype=torch.uint8, device=device),
+        torch.full((B, Hkv, S_max, D // BLOCK), 127, dtype=torch.uint8,
+                   device=device))
+
+
+def check_cache(c: MXCache) -> Tuple[int, int, int, int]:
+    """(B, Hkv, S_max, D) of a well-formed MXCache, else ValueError."""
+    if c.fmt != "mxfp8":
+        raise ValueError(f"MXCache: fmt must be 'mxfp8', got {c.fmt!r}")
+    if c.codes.dim() != 4 or c.codes.shape[3] % BLOCK:
+        raise ValueError(f"MXCache: codes must be [B, Hkv, S_max, D] with D "
+                         f"a multiple of {BLOCK}, got {tuple(c.codes.shape)}")
+    B, Hkv, S_max, D = c.codes.shape
+    if c.codes.dtype != torch.uint8 or c.scales.dtype != torch.uint8 or \
+            tuple(c.scales.shape) != (B, Hkv, S_max, D // BLOCK) or \
+            c.scales.device != c.codes.device:
+        raise ValueError(
+            f"MXCache of shape {(B, Hkv, S_max, D)}: codes and scales must "
+            f"be uint8 on one device, scales [B, Hkv, S_max, D / 32], got "
+            f"{tuple(c.scales.shape)}")
+    return B, Hkv, S_max, D
+
+
+def cache_dequantize(c: MXCache) -> torch.Tensor:
+    """bf16 [B, Hkv, S_max, D] by dequantize_ref's rule: exact for every code
+    and every in-range scale byte."""
+    B, Hkv, S_max, D = check_cache(c)
+    v = table(c.fmt).to(c.codes.device)[c.codes.long()]
+    e = c.scales.to(torch.int32) - 127
+    return torch.ldexp(v.reshape(B, Hkv, S_max, D // BLOCK, BLOCK),
+                       e[..., None]).reshape(B, Hkv, S_max, D) \
+        .to(torch.bfloat16)
+
+
+def cache_write(c: MXCache, bidx: torch.Tensor, rows: torch.Tensor,
+                x: torch.Tensor) -> None:
+    """c[bidx, :, rows] = mx_quantize(x rounded to bf16): x [..., Hkv, D]
+    with leading dims those of the broadcast (bidx, rows)."""
+    _, Hkv, _, D = check_cache(c)
+    q = mx_quantize(x.to(torch.bfloat16).reshape(-1, D), "mxfp8")
+    lead = tuple(x.shape[:-2])
+    c.codes[bidx, :, rows] = q.codes.to(c.codes.device).reshape(
+        *lead, Hkv, D)
+    c.scales[bidx, :, rows] = q.scales.to(c.codes.device).reshape(
+        *lead, Hkv, D // BLOCK)

@@ -21,6 +21,8 @@ from typing import Optional, Tuple
 
 import torch
 
+from tepdist_amd.ops import mx
+
 SQRT_2_OVER_PI = math.sqrt(2.0 / math.pi)
 
 
@@ -293,6 +295,18 @@ def attention_qkv_bwd(dout: torch.Tensor, qkv: torch.Tensor, heads: int,
     return torch.cat([back(dq), back(dk), back(dv)], dim=-1)
 
 
+def _mx_caches(name: str, k_cache, v_cache) -> bool:
+    """Whether both caches are mx.MXCache (checked); a mixed pair raises."""
+    mk, mv = isinstance(k_cache, mx.MXCache), isinstance(v_cache, mx.MXCache)
+    if mk != mv:
+        raise ValueError(f"{name}: k_cache and v_cache must both be MXCache "
+                         "or both be tensors")
+    if mk and mx.check_cache(k_cache) != mx.check_cache(v_cache):
+        raise ValueError(f"{name}: k_cache {k_cache.shape} and v_cache "
+                         f"{v_cache.shape} differ")
+    return mk
+
+
 def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
                      v_cache: torch.Tensor, positions: torch.Tensor,
                      k_new: Optional[torch.Tensor] = None,
@@ -312,6 +326,21 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
     rows; without k_new only q is rotated. fp32 math, returns [B, H, D] in
     q.dtype."""
     assert (k_new is None) == (v_new is None)
+    if _mx_caches("decode_attention", k_cache, v_cache):
+        # MXFP8 cache: the new row is rotated in fp32, rounded once to bf16
+        # and quantized by mx.mx_quantize's rule on the way in; the op is
+        # then the one below on the dequantized cache
+        if k_new is not None:
+            B, S_max = q.shape[0], k_cache.shape[2]
+            pos = positions.reshape(-1).long().clamp(0, S_max - 1).expand(B)
+            if rope_theta is not None:
+                k_new = _rope_at_f32(k_new, pos[:, None], rope_theta)
+            bidx = torch.arange(B, device=q.device)
+            mx.cache_write(k_cache, bidx, pos, k_new)
+            mx.cache_write(v_cache, bidx, pos, v_new)
+        return decode_attention(q, mx.cache_dequantize(k_cache),
+                                mx.cache_dequantize(v_cache), positions,
+                                None, None, scale, rope_theta)
     B, H, D = q.shape
     Hkv, S_max = k_cache.shape[1], k_cache.shape[2]
     assert H % Hkv == 0, (H, Hkv)
@@ -357,6 +386,21 @@ def prefill_attention(q: torch.Tensor, k_cache: torch.Tensor,
     in fp32 and each rounded once to its dtype. fp32 math, returns
     [B, T, H, D] in q.dtype."""
     assert (k_new is None) == (v_new is None)
+    if _mx_caches("prefill_attention", k_cache, v_cache):
+        # MXFP8 cache: as in decode_attention above
+        if k_new is not None:
+            B, T = q.shape[:2]
+            S_max = k_cache.shape[2]
+            p0 = positions.reshape(-1).long().clamp(0, S_max - T).expand(B)
+            rows = p0[:, None] + torch.arange(T, device=q.device)
+            if rope_theta is not None:
+                k_new = _rope_at_f32(k_new, rows[:, :, None], rope_theta)
+            bidx = torch.arange(B, device=q.device)[:, None]
+            mx.cache_write(k_cache, bidx, rows, k_new)
+            mx.cache_write(v_cache, bidx, rows, v_new)
+        return prefill_attention(q, mx.cache_dequantize(k_cache),
+                                 mx.cache_dequantize(v_cache), positions,
+                                 None, None, scale, rope_theta)
     B, T, H, D = q.shape
     Hkv, S_max = k_cache.shape[1], k_cache.shape[2]
     assert H % Hkv == 0 and 1 <= T <= S_max, (H, Hkv, T, S_max)
