@@ -30,7 +30,19 @@ mx_gemm_a8.hip), same sites, M and method. Contenders:
   "w_fused", "w_dequant"  from M = 2048, for information: the weight-only
              paths on bf16 x (ops.linear_mx; dequantize + ops.linear), a
              different model.
-`wins`: the slowest "quant_a8" window beats the fastest "library" window."""
+`wins`: the slowest "quant_a8" window beats the fastest "library" window.
+
+--act mxfp4: the W4A4 model (mxfp4 weights only; ops.linear_mx_a8 on mxfp4
+activations, the e2m1 x e2m1 instantiations), same sites, M and method, to
+profiles/linear_mx_a4.json. Contenders, all in the same windows:
+  "quant_a4" ops.mx_quantize_act(fmt="mxfp4") + ops.linear_mx_a8, as the
+             engine runs it;  "a4": the GEMM alone on x quantized beforehand;
+  "quant_a8", "a8"  the W4A8 pair above on the same weights (another model,
+             for speed only);
+  "library"  the W4A4 model on the library: the mxfp4 round trip +
+             ops.mx_dequantize + ops.linear and the engine's tail launches.
+`wins`: the slowest "quant_a4" window beats the fastest "library" window;
+`beats_a8`: it beats the fastest "quant_a8" window."""
 import json
 import os
 import statistics
@@ -208,6 +220,79 @@ def run_site_a8(model, site, N, K, form, ms):
     return rows
 
 
+def run_site_a4(model, site, N, K, form, ms):
+    torch.manual_seed(0)
+    nmat = 2 if form == "swiglu" else 1
+    q = [ops.mx_quantize(torch.randn(N, K, dtype=BF16, device="cuda")
+                         * K ** -0.5, "mxfp4") for _ in range(nmat)]
+    b = torch.randn(N, dtype=BF16, device="cuda")
+    scratch = torch.empty(N, K, dtype=BF16, device="cuda")
+    nbytes = nmat * q[0].nbytes
+    sets = max(4, -(-COLD_BYTES // nbytes))
+    qs = [[mx.MXWeight(m.codes.clone(), m.scales.clone(), m.fmt, m.shape)
+           for _ in range(sets)] for m in q]
+    rows = []
+    for M in ms:
+        x = torch.randn(M, K, dtype=BF16, device="cuda")
+        r = torch.randn(M, N, dtype=BF16, device="cuda")
+        xq = {f: ops.mx_quantize_act(x, fmt=f) for f in mx.FORMATS}
+        xr = torch.empty_like(x)
+        bias = b if "bias" in form else None
+        res = r if "res" in form else None
+        act = "gelu" if form == "bias_gelu" else "none"
+        epi = hip.skinny_epi(bias, act, res)
+
+        def tail(ys):
+            if nmat == 2:
+                return ops.swiglu(ys[0], ys[1])
+            return ys[0] if res is None else res + ys[0]
+
+        def gemm(xin, i):
+            if nmat == 2:
+                return ops.swiglu(*(hip._mx_gemm_a8_raw(
+                    xin, a[i], None, None, 0) for a in qs))
+            return hip._mx_gemm_a8_raw(xin, qs[0][i], bias, res, epi)
+
+        def quant(f):
+            return lambda i: gemm(ops.mx_quantize_act(x, out=xq[f], fmt=f), i)
+
+        fns = {
+            "quant_a4": quant("mxfp4"), "a4": lambda i: gemm(xq["mxfp4"], i),
+            "quant_a8": quant("mxfp8"), "a8": lambda i: gemm(xq["mxfp8"], i),
+            "library": lambda i: tail([ops.linear(
+                ops.mx_quantize_act(x, roundtrip=True, out=xr, fmt="mxfp4"),
+                ops.mx_dequantize(a[i], out=scratch), bias, act)
+                for a in qs]),
+        }
+        graphs, outs = {}, {}
+        for name, fn in fns.items():
+            graphs[name], outs[name] = capture(fn, sets)
+        t = {k: [] for k in graphs}
+        for _ in range(WINDOWS):
+            for k, g in graphs.items():
+                t[k].append(window_us(g, sets))
+        tile = hip.ext.mx_gemm_a8_plan(M, N, K, 4, K // 2, K // 32, K // 2,
+                                       K // 32, 0, 0, 4)[0]
+        row = {"bench": "linear_mx_a4", "model": model, "site": site,
+               "form": form, "fmt": "mxfp4", "M": M, "N": N, "K": K,
+               "tile": tile, "sets": sets, "weight_bytes": nbytes}
+        for k, v in t.items():
+            row[f"{k}_us"] = round(statistics.median(v), 2)
+            row[f"{k}_us_min_max"] = [round(min(v), 2), round(max(v), 2)]
+        row["wins"] = max(t["quant_a4"]) < min(t["library"])
+        row["beats_a8"] = max(t["quant_a4"]) < min(t["quant_a8"])
+        for k in ("a4", "a8"):
+            row[f"{k}_tflops"] = round(
+                nmat * 2.0 * M * N * K / (row[f"{k}_us"] * 1e-6) / 1e12, 1)
+        row["max_abs_diff_vs_library"] = round(
+            (outs["quant_a4"].float() - outs["library"].float())
+            .abs().max().item(), 4)
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+        del graphs, outs
+    return rows
+
+
 def main(*argv):
     def opt(name, default):
         return argv[argv.index(name) + 1].split(",") if name in argv \
@@ -216,15 +301,16 @@ def main(*argv):
     sites = opt("--sites", None)
     ms = tuple(int(m) for m in opt("--ms", MS))
     act = opt("--act", ["bf16"])[0]
-    if act not in ("bf16", "mxfp8"):
-        raise SystemExit(f"--act must be bf16 or mxfp8, got {act!r}")
+    if act not in ("bf16", "mxfp8", "mxfp4"):
+        raise SystemExit(f"--act must be bf16, mxfp8 or mxfp4, got {act!r}")
+    run = {"bf16": run_site, "mxfp8": run_site_a8, "mxfp4": run_site_a4}[act]
     skip = {a for n in ("--sites", "--ms", "--act") if n in argv
             for a in (n, argv[argv.index(n) + 1])}
     out = next((a for a in argv if a not in skip), None)
     rows = []
     for s in SITES:
         if sites is None or s[1] in sites:
-            rows += (run_site_a8 if act == "mxfp8" else run_site)(*s, ms)
+            rows += run(*s, ms)
     if out:
         with open(out, "w") as f:
             json.dump(rows, f, indent=1)

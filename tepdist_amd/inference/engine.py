@@ -88,8 +88,12 @@ normed input, then ops.swiglu); a site its plan refuses raises. Single-token
 sites the skinny MX plan covers run ops.mx_quantize_act(x, roundtrip=True)
 into a buffer allocated once, then ops.linear_decode_mx /
 ops.swiglu_linear_decode_mx as before: the same values, only the order of
-the fp32 sum differs. There is no "auto" rule yet (docs/KERNELS.md "MX
-weights x MXFP8 activations").
+the fp32 sum differs. "mxfp4" = W4A4: the same routing with e2m1 activation
+blocks (ops.mx_quantize_act(..., fmt="mxfp4"), ops.linear_mx_a8 on the
+e2m1 x e2m1 form of the scaled MFMA), valid only with weight_format="mxfp4"
+(W8A4 is not built) and mx_linear at its default; yet another model. There
+is no "auto" rule yet (docs/KERNELS.md "MX weights x MXFP8 activations", "MX
+weights x MXFP4 activations").
 
 KV cache format (kv_format=, or TEPDIST_KV_FORMAT): "bf16" (default) = every
 path above as it was. "mxfp8" = the caches are mx.MXCache (e4m3 codes and one
@@ -174,15 +178,22 @@ class Generator:
         self.mx_linear = mx_linear
         if act_format is None:
             act_format = os.environ.get("TEPDIST_ACT_FORMAT", "bf16")
-        if act_format not in ("bf16", "mxfp8"):
+        if act_format not in ("bf16",) + mx.FORMATS:
             raise ValueError(
-                f"act_format must be 'bf16' or 'mxfp8', got {act_format!r}")
+                f"act_format must be 'bf16', 'mxfp8' or 'mxfp4', "
+                f"got {act_format!r}")
         if act_format == "mxfp8" and (weight_format == "bf16"
                                       or mx_linear != "dequant"):
             raise ValueError(
                 "act_format='mxfp8' needs an MX weight_format and mx_linear "
                 f"at its default, got weight_format={weight_format!r}, "
                 f"mx_linear={mx_linear!r}")
+        if act_format == "mxfp4" and (weight_format != "mxfp4"
+                                      or mx_linear != "dequant"):
+            raise ValueError(
+                "act_format='mxfp4' needs weight_format='mxfp4' (W8A4 is not "
+                "built) and mx_linear at its default, got weight_format="
+                f"{weight_format!r}, mx_linear={mx_linear!r}")
         self.act_format = act_format
         if kv_format is None:
             kv_format = os.environ.get("TEPDIST_KV_FORMAT", "bf16")
@@ -197,7 +208,7 @@ class Generator:
             self.mxw = {id(w): mx.mx_quantize(w, weight_format) for w in ws}
             self._dq = torch.empty(max(w.numel() for w in ws),
                                    dtype=torch.bfloat16, device=ws[0].device)
-            if act_format == "mxfp8":   # round trip of a single-token input
+            if act_format != "bf16":    # round trip of a single-token input
                 self._xr = torch.empty(64 * max(w.shape[1] for w in ws),
                                        dtype=torch.bfloat16,
                                        device=ws[0].device)
@@ -247,13 +258,14 @@ class Generator:
             x2.shape[0], mw.shape[0], mw.shape[1], mx.bits(mw.fmt), epi)
 
     def _roundtrip(self, x2):
-        """The MXFP8 round trip of x2 [M, K] in the buffer of the
+        """The act_format round trip of x2 [M, K] in the buffer of the
         single-token sites (M <= 64 there): valid until the next call."""
         M, K = x2.shape
         out = self._xr[:M * K].view(M, K) \
             if M * K <= self._xr.numel() and x2.dtype == self._xr.dtype \
             else None
-        return ops.mx_quantize_act(x2, roundtrip=True, out=out)
+        return ops.mx_quantize_act(x2, roundtrip=True, out=out,
+                                   fmt=self.act_format)
 
     def _dequantized(self, mw, dtype):
         """bf16 weight of mw in the shared scratch buffer: valid until the
@@ -346,12 +358,13 @@ class Generator:
             x2 = x.reshape(-1, x.shape[-1])
             r2 = None if residual is None else \
                 residual.reshape(-1, w.shape[0])
-            if self.act_format == "mxfp8":
+            if self.act_format != "bf16":
                 if decode and self._mx_site(x2, mw, bias, act, r2):
                     y = ops.linear_decode_mx(self._roundtrip(x2), mw, bias,
                                              act, r2)
                 else:
-                    y = ops.linear_mx_a8(x2, mw, bias, act, r2)
+                    y = ops.linear_mx_a8(x2, mw, bias, act, r2,
+                                         self.act_format)
                 return y.reshape(*x.shape[:-1], w.shape[0]) \
                     if residual is None else y.reshape(residual.shape)
             if decode and self._mx_site(x2, mw, bias, act, r2):
@@ -473,11 +486,11 @@ class Generator:
         B, T, d = x.shape
         hn = ops.rmsnorm(x.reshape(B * T, d), blk.ln2_g, cfg.rms_eps)
         mg, mu = self.mxw.get(id(blk.w_gate)), self.mxw.get(id(blk.w_up))
-        if mg is not None and self.act_format == "mxfp8":
+        if mg is not None and self.act_format != "bf16":
             if T == 1 and self._mx_site(hn, mg, mw_up=mu):
                 h = ops.swiglu_linear_decode_mx(self._roundtrip(hn), mg, mu)
             else:               # one quantization, shared by gate and up
-                xq = ops.mx_quantize_act(hn)
+                xq = ops.mx_quantize_act(hn, fmt=self.act_format)
                 h = ops.swiglu(ops.linear_mx_a8(xq, mg),
                                ops.linear_mx_a8(xq, mu))
         elif mg is not None and T == 1 and self._mx_site(hn, mg, mw_up=mu):

@@ -180,52 +180,74 @@ PYBIND11_MODULE(_tepdist_hip, m) {
   m.def("mx_act_quant", [](uintptr_t x, uintptr_t codes, uintptr_t scales,
                            uintptr_t out, int M, int K, int64_t ldx,
                            int64_t ldc, int64_t lds, int64_t ldo,
-                           uintptr_t stream) {
+                           uintptr_t stream, int x_bits) {
     mx_act_quant(reinterpret_cast<void*>(x), reinterpret_cast<void*>(codes),
                  reinterpret_cast<void*>(scales),
                  reinterpret_cast<void*>(out), M, K, ldx, ldc, lds, ldo,
-                 S(stream));
+                 S(stream), x_bits);
     check_launch();
-  });
+  }, py::arg("x"), py::arg("codes"), py::arg("scales"), py::arg("out"),
+     py::arg("M"), py::arg("K"), py::arg("ldx"), py::arg("ldc"),
+     py::arg("lds"), py::arg("ldo"), py::arg("stream"),
+     py::arg("x_bits") = 8);
 
-  // the quantizer's rule on the host: (scale byte, e4m3 codes) of one block
-  // of bf16 bit patterns — the lines the kernel runs, no GPU
-  m.def("mx_act_quant_block", [](const std::vector<unsigned>& bits) {
+  // the quantizer's rule on the host: (scale byte, codes) of one block of
+  // bf16 bit patterns — the lines the kernel runs, no GPU. bits = 8: one
+  // e4m3 code per element; bits = 4: the packed e2m1 bytes, even k low
+  m.def("mx_act_quant_block", [](const std::vector<unsigned>& pat, int bits) {
+    if (bits != 8 && bits != 4)
+      throw std::invalid_argument("mx_act_quant_block: bits must be 8 or 4");
     unsigned amax = 0;
-    for (unsigned b : bits) amax = std::max(amax, b & 0x7fffu);
-    const unsigned byte = mxq_scale_byte(amax);
+    for (unsigned b : pat) amax = std::max(amax, b & 0x7fffu);
     std::vector<unsigned> codes;
-    for (unsigned b : bits) codes.push_back(mxq_e4m3(b & 0xffffu, byte));
+    if (bits == 8) {
+      const unsigned byte = mxq_scale_byte(amax);
+      for (unsigned b : pat) codes.push_back(mxq_e4m3(b & 0xffffu, byte));
+      return py::make_tuple(byte, codes);
+    }
+    if (pat.size() % 2)
+      throw std::invalid_argument("mx_act_quant_block: an odd block");
+    const unsigned byte = mxq_scale_byte4(amax);
+    for (size_t k = 0; k < pat.size(); k += 2)
+      codes.push_back(mxq_e2m1(pat[k] & 0xffffu, byte) |
+                      (mxq_e2m1(pat[k + 1] & 0xffffu, byte) << 4));
     return py::make_tuple(byte, codes);
-  });
+  }, py::arg("pattern"), py::arg("bits") = 8);
 
   m.def("mx_gemm_a8", [](uintptr_t xcodes, uintptr_t xscales, uintptr_t codes,
                          uintptr_t scales, uintptr_t bias, uintptr_t res,
                          uintptr_t y, int M, int N, int K, int bits,
                          int64_t ldxc, int64_t ldxs, int64_t ldc, int64_t lds,
                          int64_t ldr, int64_t ldy, int epi, int tile,
-                         uintptr_t stream) {
+                         uintptr_t stream, int x_bits) {
     mx_gemm_a8(reinterpret_cast<void*>(xcodes),
                reinterpret_cast<void*>(xscales),
                reinterpret_cast<void*>(codes), reinterpret_cast<void*>(scales),
                reinterpret_cast<void*>(bias), reinterpret_cast<void*>(res),
                reinterpret_cast<void*>(y), M, N, K, bits, ldxc, ldxs, ldc,
-               lds, ldr, ldy, epi, tile, S(stream));
+               lds, ldr, ldy, epi, tile, S(stream), x_bits);
     check_launch();
-  });
+  }, py::arg("xcodes"), py::arg("xscales"), py::arg("codes"),
+     py::arg("scales"), py::arg("bias"), py::arg("res"), py::arg("y"),
+     py::arg("M"), py::arg("N"), py::arg("K"), py::arg("bits"),
+     py::arg("ldxc"), py::arg("ldxs"), py::arg("ldc"), py::arg("lds"),
+     py::arg("ldr"), py::arg("ldy"), py::arg("epi"), py::arg("tile"),
+     py::arg("stream"), py::arg("x_bits") = 8);
 
   // (tile, stages, blocks, why_not) — host-only, no GPU
   m.def("mx_gemm_a8_plan", [](int M, int N, int K, int bits,
                               int64_t ld_wcodes, int64_t ld_wscales,
                               int64_t ld_xcodes, int64_t ld_xscales, int epi,
-                              int tile) {
-    const MxGemmPlan p = mx_gemm_a8_plan(M, N, K, bits, ld_wcodes, ld_wscales,
-                                         ld_xcodes, ld_xscales, epi, tile);
+                              int tile, int x_bits) {
+    const MxGemmPlan p =
+        mx_gemm_a8_plan(M, N, K, bits, ld_wcodes, ld_wscales, ld_xcodes,
+                        ld_xscales, epi, tile, x_bits);
     return py::make_tuple(p.tile, p.stages, p.blocks,
                           p.why_not ? p.why_not : "");
   }, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("bits"),
      py::arg("ld_wcodes"), py::arg("ld_wscales"), py::arg("ld_xcodes"),
-     py::arg("ld_xscales"), py::arg("epi") = 0, py::arg("tile") = 0);
+     py::arg("ld_xscales"), py::arg("epi") = 0, py::arg("tile") = 0,
+     py::arg("x_bits") = 8);
 
   m.def("transpose", [](uintptr_t in, uintptr_t out, int R, int C,
                         int64_t si, int64_t so, int batch,

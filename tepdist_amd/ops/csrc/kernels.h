@@ -94,25 +94,27 @@ void mx_gemm(const void* x, const void* codes, const void* scales,
              int bits, int64_t ldx, int64_t ldc, int64_t lds, int64_t ldr,
              int64_t ldy, int epi, int tile, hipStream_t stream);
 
-// --- MX weights x MXFP8 activations (mx_act_quant.hip, mx_gemm_a8.hip) --------
+// --- MX weights x MX activations (mx_act_quant.hip, mx_gemm_a8.hip) -----------
 // x[M, K] bf16 (row stride ldx elements, K % 32 == 0) quantized by the rule of
-// ops/mx.py's mx_quantize(x, "mxfp8"), bit for bit. Either codes [M, K] e4m3
-// (row stride ldc bytes) and scales [M, K / 32] e8m0 (lds bytes) are written
-// and out is null, or out [M, K] bf16 (ldo elements) gets the dequantized
-// values and codes / scales are null. One launch, no workspace.
+// ops/mx.py's mx_quantize(x, "mxfp8" | "mxfp4") for x_bits 8 | 4, bit for
+// bit. Either codes [M, K] e4m3 or [M, K / 2] e2m1 (row stride ldc bytes) and
+// scales [M, K / 32] e8m0 (lds bytes) are written and out is null, or out
+// [M, K] bf16 (ldo elements) gets the dequantized values and codes / scales
+// are null. One launch, no workspace.
 void mx_act_quant(const void* x, void* codes, void* scales, void* out, int M,
                   int K, int64_t ldx, int64_t ldc, int64_t lds, int64_t ldo,
-                  hipStream_t stream);
+                  hipStream_t stream, int x_bits = 8);
 // y[M, N] = epi(dq(Xq)[M, K] @ dq(W)[N, K]^T) on the scaled MFMA, any M >= 1,
-// K % 128 == 0. Xq: e4m3 codes (row stride ldxc bytes) and scale bytes (ldxs);
-// W, bias, res, y, epi and tile as mx_gemm. One launch, no workspace, no
+// K % 128 == 0. Xq: e4m3 codes (x_bits 8) or, with e2m1 weights, e2m1 codes
+// (x_bits 4), row stride ldxc bytes, and scale bytes (ldxs); W, bias, res, y, epi and tile as mx_gemm. One launch, no workspace, no
 // atomics. Throws with mx_gemm_a8_plan()'s reason when the call is not
 // covered.
 void mx_gemm_a8(const void* xcodes, const void* xscales, const void* codes,
                 const void* scales, const void* bias, const void* res,
                 void* y, int M, int N, int K, int bits, int64_t ldxc,
                 int64_t ldxs, int64_t ldc, int64_t lds, int64_t ldr,
-                int64_t ldy, int epi, int tile, hipStream_t stream);
+                int64_t ldy, int epi, int tile, hipStream_t stream,
+                int x_bits = 8);
 
 // --- Transpose -------------------------------------------------------------
 // out[c][r] = in[r][c] per batch (strides in elements).

@@ -23,6 +23,18 @@
 // and stored as one dword if the scale rows are 4-byte aligned; otherwise
 // lane 0 of each quad stores its byte. Rows >= M are never touched (no thread
 // exists for them). No LDS, no atomics, one launch.
+//
+// MXFP4 (XBITS = 4): mx_quantize(x, "mxfp4") by mxq_scale_byte4 / mxq_e2m1 of
+// the same header (scale byte = clamp(biased exponent of the amax - 2, 2,
+// 252), elements saturated at +-6, ties to the even code), codes [M, K / 2]
+// with even k in the low nibble. Same split, load, amax and scale stores; a
+// lane's 8 codes are one dword, and the quad's 16 bytes leave as two 8-byte
+// stores: each even lane takes its odd neighbour's dword by one quad_perm DPP
+// and stores the pair. The alternative, one 16-byte store by the quad's lane
+// 0, needs three DPP moves and 16-byte-aligned code rows; the pair store
+// keeps the 8-byte rule of the mxfp8 codes (the same out= views are taken)
+// and a wave still writes 256 contiguous bytes. The round trip is dq_fp4 of
+// mx_dequant.h: an e2m1 element times an in-range scale is exact in bf16.
 
 #include <stdexcept>
 
@@ -43,7 +55,7 @@ DEV_INLINE unsigned mxq_quad(unsigned v) {
                                                true);
 }
 
-template <bool ROUNDTRIP>
+template <bool ROUNDTRIP, int XBITS>
 __launch_bounds__(MXQ_THREADS) __global__
 void mx_act_quant_kernel(const bf16_t* __restrict__ x,
                          uint8_t* __restrict__ codes,
@@ -65,23 +77,36 @@ void mx_act_quant_kernel(const bf16_t* __restrict__ x,
   }
   amax = max(amax, mxq_quad<0xB1>(amax));  // quad_perm [1, 0, 3, 2]
   amax = max(amax, mxq_quad<0x4E>(amax));  // quad_perm [2, 3, 0, 1]
-  const unsigned byte = mxq_scale_byte(amax);
+  const unsigned byte =
+      XBITS == 4 ? mxq_scale_byte4(amax) : mxq_scale_byte(amax);
 
-  unsigned q[2];
+  unsigned q[2] = {0, 0};  // XBITS == 4: q[0] alone, eight nibbles
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const unsigned two = mxq_e4m3(v[j] & 0xffffu, byte) |
-                         (mxq_e4m3(v[j] >> 16, byte) << 8);
-    if (j & 1) q[j >> 1] |= two << 16;
-    else q[j >> 1] = two;
+    if constexpr (XBITS == 4) {
+      q[0] |= (mxq_e2m1(v[j] & 0xffffu, byte) |
+               (mxq_e2m1(v[j] >> 16, byte) << 4)) << (8 * j);
+    } else {
+      const unsigned two = mxq_e4m3(v[j] & 0xffffu, byte) |
+                           (mxq_e4m3(v[j] >> 16, byte) << 8);
+      q[j >> 1] |= two << (16 * (j & 1));
+    }
   }
 
   if constexpr (ROUNDTRIP) {
     *reinterpret_cast<bf16x8*>(out + row * ldo + 8 * c) =
-        dq_fp8(q[0], q[1], mx_scale(byte));
+        XBITS == 4 ? dq_fp4(q[0], mx_scale(byte))
+                   : dq_fp8(q[0], q[1], mx_scale(byte));
   } else {
-    *reinterpret_cast<uint2*>(codes + row * ldc + 8 * c) =
-        make_uint2(q[0], q[1]);
+    if constexpr (XBITS == 4) {
+      const unsigned odd = mxq_quad<0xF5>(q[0]);  // quad_perm [1, 1, 3, 3]
+      if ((threadIdx.x & 1) == 0)
+        *reinterpret_cast<uint2*>(codes + row * ldc + 4 * c) =
+            make_uint2(q[0], odd);
+    } else {
+      *reinterpret_cast<uint2*>(codes + row * ldc + 8 * c) =
+          make_uint2(q[0], q[1]);
+    }
     uint8_t* sp = scales + row * lds + (c >> 2);
     if (dword_scales) {
       unsigned g = byte | ((unsigned)__shfl_down((int)byte, 4, 64) << 8);
@@ -97,10 +122,12 @@ void mx_act_quant_kernel(const bf16_t* __restrict__ x,
 
 void mx_act_quant(const void* x, void* codes, void* scales, void* out, int M,
                   int K, int64_t ldx, int64_t ldc, int64_t lds, int64_t ldo,
-                  hipStream_t stream) {
+                  hipStream_t stream, int x_bits) {
   auto a = [](const void* p, int n) {
     return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0;
   };
+  if (x_bits != 8 && x_bits != 4)
+    throw std::runtime_error("mx_act_quant: x_bits must be 8 or 4");
   if (M < 1 || K < 32 || K % 32)
     throw std::runtime_error(
         "mx_act_quant: M must be positive and K a positive multiple of 32");
@@ -115,10 +142,12 @@ void mx_act_quant(const void* x, void* codes, void* scales, void* out, int M,
   if (roundtrip && (!a(out, 16) || ldo < K || (ldo & 7)))
     throw std::runtime_error(
         "mx_act_quant: out needs a 16-byte-aligned base and rows");
-  if (!roundtrip && (!a(codes, 8) || ldc < K || (ldc & 7) || lds < K / 32))
+  if (!roundtrip && (!a(codes, 8) || ldc < K * x_bits / 8 || (ldc & 7) ||
+                     lds < K / 32))
     throw std::runtime_error(
-        "mx_act_quant: codes need an 8-byte-aligned base and rows, scale "
-        "rows K / 32 bytes");
+        "mx_act_quant: codes need an 8-byte-aligned base and rows (a byte "
+        "stride that is a multiple of 8, at least K * bits / 8), scale rows "
+        "K / 32 bytes");
   const int K8 = K / 8;
   const int64_t total = (int64_t)M * K8;
   const int64_t blocks = (total + MXQ_THREADS - 1) / MXQ_THREADS;
@@ -126,15 +155,19 @@ void mx_act_quant(const void* x, void* codes, void* scales, void* out, int M,
     throw std::runtime_error("mx_act_quant: M * K is too large for one grid");
   const int dword = !roundtrip && K % 128 == 0 && a(scales, 4) &&
                     (lds & 3) == 0;
-#define MXQ_GO(RT)                                                          \
-  hipLaunchKernelGGL((mx_act_quant_kernel<RT>), dim3((unsigned)blocks),     \
+#define MXQ_GO(RT, XX)                                                      \
+  hipLaunchKernelGGL((mx_act_quant_kernel<RT, XX>), dim3((unsigned)blocks), \
                      dim3(MXQ_THREADS), 0, stream,                          \
                      static_cast<const bf16_t*>(x),                         \
                      static_cast<uint8_t*>(codes),                          \
                      static_cast<uint8_t*>(scales),                         \
                      static_cast<bf16_t*>(out), total, K8, ldx, ldc, lds,   \
                      ldo, dword)
-  if (roundtrip) MXQ_GO(true); else MXQ_GO(false);
+  if (x_bits == 4) {
+    if (roundtrip) MXQ_GO(true, 4); else MXQ_GO(false, 4);
+  } else {
+    if (roundtrip) MXQ_GO(true, 8); else MXQ_GO(false, 8);
+  }
 #undef MXQ_GO
 }
 

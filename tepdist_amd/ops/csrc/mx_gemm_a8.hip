@@ -1,8 +1,9 @@
-// GEMM on OCP MX weights and MXFP8 activations for gfx950, on the scaled
-// matrix instruction v_mfma_scale_f32_16x16x128_f8f6f4:
+// GEMM on OCP MX weights and MX activations for gfx950, on the scaled matrix
+// instruction v_mfma_scale_f32_16x16x128_f8f6f4:
 //   y[M, N] = epi(dq(Xq)[M, K] . dq(W)[N, K]^T),  M >= 1, any N, K % 128 == 0,
-//   Xq e4m3 codes, W e2m1 or e4m3 codes, one e8m0 scale byte per 32 k of a row
-//   on both sides (the interchange layout of ops/mx.py, nothing repacked);
+//   Xq e4m3 codes (W e2m1 or e4m3: W4A8, W8A8) or e2m1 codes (W e2m1 only:
+//   W4A4, the instruction's double-rate form), one e8m0 scale byte per 32 k
+//   of a row on both sides (the interchange layout of ops/mx.py, nothing repacked);
 //   bias / residual / y bf16, fp32 accumulate, one rounding.
 // Neither operand is ever dequantized: codes and scale bytes go from memory to
 // LDS to the instruction's registers as they lie. No split-K, no workspace,
@@ -10,7 +11,7 @@
 //
 // Block and wave. 256 threads, 2 x 2 waves; wave (wm, wn) owns WM token
 // fragments x WN weight fragments. Weights are the A operand (cbsz 4 = e2m1
-// or 0 = e4m3), activations B (blgp 0), so D is [n][m] and a lane's four
+// or 0 = e4m3), activations B (blgp 0 = e4m3 or 4 = e2m1), so D is [n][m] and a lane's four
 // accumulator elements are four consecutive n of one token, as in mx_gemm.hip
 // and the skinny kernels. Block tile (32 WM) x (32 WN): 128 x 128 and 64 x 64.
 //
@@ -20,7 +21,10 @@
 // lane 16 g + i holds row i, k 16 g .. 16 g + 15 in V0-3 and k 64 + 16 g ..
 // 64 + 16 g + 15 in V4-7 (the instruction is two passes of 64 k). e2m1, 4
 // VGPRs (the upper four are not read under cbsz 4): lane 16 g + i holds row
-// i, k 32 g .. 32 g + 31. Scales, either width: the scale of row i and MX
+// i, k 32 g .. 32 g + 31. The B operand under blgp 4 mirrors the A operand
+// under cbsz 4, lane map, nibble order (even k low) and scale lane alike: the
+// one-hot placement test of the a4 suite was run on the device against this
+// assumption and holds it. Scales, either width: the scale of row i and MX
 // block b (k 32 b .. 32 b + 31) is the low byte of lane 16 b + i's scale
 // VGPR (op_sel 0 on both sides); for e4m3 that lane holds only half of the
 // block's elements, which is of no concern to the code: each lane reads the
@@ -29,7 +33,15 @@
 // LDS stage (three of them), every image staged by global_load_lds with the
 // swizzle applied to the per-lane SOURCE address (the destination of a wave's
 // DMA is lane-linear):
-//  x codes [BM][128] bytes, 8 slots of 16 B a row. Two rows fill the 64
+//  x codes, e2m1: [BM][64] bytes, the image, rule and single read of the
+//          e2m1 weight rows below (four rows fill the banks, slot s of row r
+//          holds bytes 16 (s ^ ((r >> 2) & 3)), the fragment is one
+//          ds_read_b128 at slot g ^ (i >> 2) of row 16 mt + i, and the 16
+//          lanes of a group hit unit 4 (i & 3) + (g ^ (i >> 2)) of the 16
+//          units of the bank row: i & 3 picks the quarter, and within a
+//          quarter i >> 2 runs over 0 .. 3, so g ^ (i >> 2) does: all
+//          different). DMA rows are 64 B, four lanes a row.
+//  x codes, e4m3: [BM][128] bytes, 8 slots of 16 B a row. Two rows fill the 64
 //          banks, so rows i and i + 2 collide unswizzled; slot s of row r
 //          holds bytes 16 (s ^ ((r >> 1) & 7)). A fragment is two
 //          ds_read_b128 (q = 0, 1) at slots (g + 4 q) ^ (i >> 1) of row 16 mt
@@ -46,10 +58,18 @@
 //          one ds_read_u8: 16 consecutive dwords per group, 16 different
 //          banks; the four groups of a row share a dword (broadcast).
 // A stage is 33 KiB at 128 / e4m3 (25 KiB e2m1), 16.5 KiB at 64 (12.5 KiB):
-// 99 of the 160 KiB at the 128-tile, three blocks per CU at the 64-tile.
+// 99 of the 160 KiB at the 128-tile, three blocks per CU at the 64-tile. With
+// e2m1 on both sides it is 17 KiB at 128 and 8.5 KiB at 64: 51 KiB, three
+// blocks per CU at the 128-tile.
+//
+// K-tile of the e2m1 x e2m1 form: 128 k, three stages, the loop below as it
+// is, so one barrier per WM * WN half-length MFMAs and 64-byte DMA rows. A
+// 256-k tile (two instructions per fragment pair and stage, a tail stage for
+// odd K / 128) would halve both counts per MFMA; it is not built, and the
+// documentation lists it as not measured.
 //
 // Pipeline (the protocol of mx_gemm.hip). Per stage every wave issues the
-// same OPS DMAs: BM / 32 of x codes, BN * RB / 4096 of w codes and one 4-byte
+// same OPS DMAs: BM * XRB / 4096 of x codes (XRB = 128 or 64), BN * RB / 4096 of w codes and one 4-byte
 // DMA of scales: 64 rows a wave out of the BN + BM; at 128 waves 0, 1 take
 // the weight rows and 2, 3 the token rows, at 64 waves 0 and 2 both take the
 // weight rows and 1 and 3 the token rows (the same bytes to the same place,
@@ -105,7 +125,7 @@ DEV_INLINE void mxa_wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-template <int BITS, int WM, int WN>
+template <int BITS, int XBITS, int WM, int WN>
 __launch_bounds__(MXA_THREADS) __global__
 void mx_gemm_a8_kernel(const uint8_t* __restrict__ xcodes,
                        const uint8_t* __restrict__ xscales,
@@ -117,14 +137,18 @@ void mx_gemm_a8_kernel(const uint8_t* __restrict__ xcodes,
                        int64_t ldc, int64_t lds, int64_t ldr, int64_t ldy,
                        int epi) {
   constexpr int BM = 32 * WM, BN = 32 * WN;
-  constexpr int KT = mx_tiled::KTILE;    // k, and bytes of an x code row
+  static_assert(XBITS == 8 || (XBITS == 4 && BITS == 4), "W8A4 is not built");
+  constexpr int KT = mx_tiled::KTILE;    // k of a tile
   constexpr int RB = 16 * BITS;          // w code bytes of a row and K-tile
   constexpr int SL = RB / 16;            // 16-byte slots of a w code row
   constexpr int WQ = BITS / 4;           // 16-byte reads of one w MX block
-  constexpr int XC = BM * 8 / MXA_THREADS;   // x code DMAs per thread
-  constexpr int CC = BN * SL / MXA_THREADS;  // w code DMAs
+  constexpr int XRB = 16 * XBITS;        // x code bytes of a row and K-tile
+  constexpr int XSL = XRB / 16;          // 16-byte slots of an x code row
+  constexpr int XQ = XBITS / 4;          // 16-byte reads of one x fragment
+  constexpr int XC = BM * XSL / MXA_THREADS;  // x code DMAs per thread
+  constexpr int CC = BN * SL / MXA_THREADS;   // w code DMAs
   constexpr int OPS = XC + CC + 1;       // DMAs per wave and stage
-  constexpr int XB = BM * KT, CB = BN * RB, SB = (BN + BM) * 4;
+  constexpr int XB = BM * XRB, CB = BN * RB, SB = (BN + BM) * 4;
   constexpr int STAGE = XB + CB + SB;
   constexpr int LDI = BN + 8;            // output image row, elements
   static_assert(BM * LDI * 2 <= mx_tiled::STAGES * STAGE, "image fits");
@@ -144,9 +168,9 @@ void mx_gemm_a8_kernel(const uint8_t* __restrict__ xcodes,
   const uint8_t* xg[XC];
 #pragma unroll
   for (int c = 0; c < XC; ++c) {
-    const int row = (c * MXA_THREADS + tid) >> 3, slot = tid & 7;
-    xg[c] = xcodes + (int64_t)min(m0 + row, M - 1) * ldxc +
-            16 * (slot ^ ((row >> 1) & 7));
+    const int row = (c * MXA_THREADS + tid) / XSL, slot = tid % XSL;
+    const int sw = XBITS == 4 ? (row >> 2) & 3 : (row >> 1) & 7;
+    xg[c] = xcodes + (int64_t)min(m0 + row, M - 1) * ldxc + 16 * (slot ^ sw);
   }
   const uint8_t* cg[CC];
 #pragma unroll
@@ -167,7 +191,7 @@ void mx_gemm_a8_kernel(const uint8_t* __restrict__ xcodes,
     uint8_t* st = smem + slot * STAGE + wid * 1024;  // wave-uniform
 #pragma unroll
     for (int c = 0; c < XC; ++c)
-      __builtin_amdgcn_global_load_lds((glds_src_t)(xg[c] + (int64_t)t * KT),
+      __builtin_amdgcn_global_load_lds((glds_src_t)(xg[c] + (int64_t)t * XRB),
                                        (glds_dst_t)(st + c * 4096), 16, 0, 0);
 #pragma unroll
     for (int c = 0; c < CC; ++c)
@@ -186,12 +210,12 @@ void mx_gemm_a8_kernel(const uint8_t* __restrict__ xcodes,
     for (int mt = 0; mt < WM; ++mt) acc[t][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   // this lane's fragment rows inside a stage
-  const int xoff = (wm * 16 * WM + i) * KT;
+  const int xoff = (wm * 16 * WM + i) * XRB;
   const int coff = XB + (wn * 16 * WN + i) * RB;
   const int wsoff = XB + CB + (wn * 16 * WN + i) * 4 + g;
   const int xsoff = XB + CB + (BN + wm * 16 * WM + i) * 4 + g;
-  const int xsw = (i >> 1) & 7;
-  const int csw = BITS == 4 ? (i >> 2) & 3 : xsw;
+  const int xsw = XBITS == 4 ? (i >> 2) & 3 : (i >> 1) & 7;
+  const int csw = BITS == 4 ? (i >> 2) & 3 : (i >> 1) & 7;
 
   auto compute = [&](int slot) {
     const uint8_t* st = smem + slot * STAGE;
@@ -210,17 +234,19 @@ void mx_gemm_a8_kernel(const uint8_t* __restrict__ xcodes,
     }
 #pragma unroll
     for (int mt = 0; mt < WM; ++mt) {
-      const uint8_t* xr = st + xoff + mt * 16 * KT;
-      const u32x4 a = *reinterpret_cast<const u32x4*>(xr + 16 * (g ^ xsw));
-      const u32x4 b =
-          *reinterpret_cast<const u32x4*>(xr + 16 * ((g + 4) ^ xsw));
-      const i32x8 xf = {(int)a[0], (int)a[1], (int)a[2], (int)a[3],
-                        (int)b[0], (int)b[1], (int)b[2], (int)b[3]};
+      const uint8_t* xr = st + xoff + mt * 16 * XRB;
+      u32x4 r[2] = {u32x4{0, 0, 0, 0}, u32x4{0, 0, 0, 0}};
+#pragma unroll
+      for (int q = 0; q < XQ; ++q)
+        r[q] = *reinterpret_cast<const u32x4*>(xr + 16 * ((g + 4 * q) ^ xsw));
+      const i32x8 xf = {(int)r[0][0], (int)r[0][1], (int)r[0][2], (int)r[0][3],
+                        (int)r[1][0], (int)r[1][1], (int)r[1][2], (int)r[1][3]};
       const int xs = st[xsoff + mt * 64];
 #pragma unroll
       for (int t = 0; t < WN; ++t)
         acc[t][mt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-            wf[t], xf, acc[t][mt], BITS == 4 ? 4 : 0, 0, 0, ws[t], 0, xs);
+            wf[t], xf, acc[t][mt], BITS == 4 ? 4 : 0, XBITS == 4 ? 4 : 0, 0,
+            ws[t], 0, xs);
     }
   };
 
@@ -312,9 +338,10 @@ void mx_gemm_a8(const void* xcodes, const void* xscales, const void* codes,
                 const void* scales, const void* bias, const void* res,
                 void* y, int M, int N, int K, int bits, int64_t ldxc,
                 int64_t ldxs, int64_t ldc, int64_t lds, int64_t ldr,
-                int64_t ldy, int epi, int tile, hipStream_t stream) {
+                int64_t ldy, int epi, int tile, hipStream_t stream,
+                int x_bits) {
   const MxGemmPlan p =
-      mx_gemm_a8_plan(M, N, K, bits, ldc, lds, ldxc, ldxs, epi, tile);
+      mx_gemm_a8_plan(M, N, K, bits, ldc, lds, ldxc, ldxs, epi, tile, x_bits);
   if (p.why_not)
     throw std::runtime_error(std::string("mx_gemm_a8: ") + p.why_not);
   const bool has_bias =
@@ -333,8 +360,8 @@ void mx_gemm_a8(const void* xcodes, const void* xscales, const void* codes,
   if (has_res && ldr < N) throw std::runtime_error("mx_gemm_a8: ldr < N");
   if (ldy < N) throw std::runtime_error("mx_gemm_a8: ldy < N");
 
-#define MXA_GO(BB, WW)                                                      \
-  hipLaunchKernelGGL((mx_gemm_a8_kernel<BB, WW, WW>), dim3(p.blocks),       \
+#define MXA_GO(BB, XX, WW)                                                  \
+  hipLaunchKernelGGL((mx_gemm_a8_kernel<BB, XX, WW, WW>), dim3(p.blocks),   \
                      dim3(MXA_THREADS), 0, stream,                          \
                      static_cast<const uint8_t*>(xcodes),                   \
                      static_cast<const uint8_t*>(xscales),                  \
@@ -344,10 +371,12 @@ void mx_gemm_a8(const void* xcodes, const void* xscales, const void* codes,
                      static_cast<const bf16_t*>(res),                       \
                      static_cast<bf16_t*>(y), M, N, K, ldxc, ldxs, ldc,     \
                      lds, ldr, ldy, epi)
-  if (bits == 4) {
-    if (p.tile == 128) MXA_GO(4, 4); else MXA_GO(4, 2);
+  if (x_bits == 4) {  // the plan has refused it with e4m3 weights
+    if (p.tile == 128) MXA_GO(4, 4, 4); else MXA_GO(4, 4, 2);
+  } else if (bits == 4) {
+    if (p.tile == 128) MXA_GO(4, 8, 4); else MXA_GO(4, 8, 2);
   } else {
-    if (p.tile == 128) MXA_GO(8, 4); else MXA_GO(8, 2);
+    if (p.tile == 128) MXA_GO(8, 8, 4); else MXA_GO(8, 8, 2);
   }
 #undef MXA_GO
 }

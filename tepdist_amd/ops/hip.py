@@ -424,20 +424,22 @@ def mx_gemm_auto(M: int, N: int, K: int, bits: int, epi: int) -> bool:
     return M * N <= 1 << 22
 
 
-# MX weights x MXFP8 activations (csrc/mx_act_quant.hip, csrc/mx_gemm_a8.hip):
-# the activation quantizer and the GEMM on the scaled MFMA, which reads both
-# operands as codes and scale bytes. Coverage and tile come from
+# MX weights x MXFP8 or MXFP4 activations (csrc/mx_act_quant.hip, csrc/
+# mx_gemm_a8.hip): the activation quantizer and the GEMM on the scaled MFMA,
+# which reads both operands as codes and scale bytes. Coverage and tile come from
 # csrc/mx_gemm_a8_plan.h (ext.mx_gemm_a8_plan).
 
-def mx_quantize_act(x: torch.Tensor, roundtrip: bool = False, out=None):
+def mx_quantize_act(x: torch.Tensor, roundtrip: bool = False, out=None,
+                    fmt: str = "mxfp8"):
     """x [..., K] bf16 (K % 32 == 0, rows strided, last dim contiguous)
-    quantized as mx.mx_quantize(x, "mxfp8"), bit for bit, in one launch.
-    roundtrip=False: an MXWeight(codes [M, K], scales [M, K / 32], "mxfp8",
-    (M, K)) with M the product of the leading dims; out = such an MXWeight to
-    write into (uint8 views, last dim contiguous). roundtrip=True: the
-    dequantized values as bf16 of x's shape; out = a bf16 tensor of x's shape
-    whose rows flatten to [M, K] as a view."""
+    quantized as mx.mx_quantize(x, fmt), bit for bit, in one launch.
+    roundtrip=False: an MXWeight(codes [M, K] or, "mxfp4", [M, K / 2], scales
+    [M, K / 32], fmt, (M, K)) with M the product of the leading dims; out =
+    such an MXWeight to write into (uint8 views, last dim contiguous).
+    roundtrip=True: the dequantized values as bf16 of x's shape; out = a bf16
+    tensor of x's shape whose rows flatten to [M, K] as a view."""
     from tepdist_amd.ops import mx
+    xb = mx.bits(fmt)
     K = x.shape[-1] if x.dim() else 0
     if x.dtype != BF16 or x.dim() < 1 or K < 32 or K % 32 or not x.is_cuda \
             or x.stride(-1) != 1:
@@ -458,36 +460,36 @@ def mx_quantize_act(x: torch.Tensor, roundtrip: bool = False, out=None):
             raise ValueError("mx_quantize_act: out must be bf16 of x's shape "
                              "with a 16-byte-aligned base and rows")
         ext.mx_act_quant(x2.data_ptr(), 0, 0, o2.data_ptr(), M, K,
-                         x2.stride(0), 0, 0, o2.stride(0), _stream())
+                         x2.stride(0), 0, 0, o2.stride(0), _stream(), xb)
         return out
     if out is None:
         out = mx.MXWeight(
-            torch.empty(M, K, dtype=torch.uint8, device=x.device),
+            torch.empty(M, K * xb // 8, dtype=torch.uint8, device=x.device),
             torch.empty(M, K // 32, dtype=torch.uint8, device=x.device),
-            "mxfp8", (M, K))
+            fmt, (M, K))
     c, s = out.codes, out.scales
-    if out.fmt != "mxfp8" or tuple(out.shape) != (M, K) or \
+    if out.fmt != fmt or tuple(out.shape) != (M, K) or \
             mx.check(out) != (M, K) or c.stride(1) != 1 or s.stride(1) != 1 \
             or not c.is_cuda or not s.is_cuda or c.data_ptr() % 8 or \
             c.stride(0) % 8:
-        raise ValueError(f"mx_quantize_act: out must be an mxfp8 MXWeight of "
+        raise ValueError(f"mx_quantize_act: out must be an {fmt} MXWeight of "
                          f"shape {(M, K)} on the device with 8-byte-aligned "
-                         "code rows")
+                         "code rows (base and byte stride multiples of 8)")
     ext.mx_act_quant(x2.data_ptr(), c.data_ptr(), s.data_ptr(), 0, M, K,
-                     x2.stride(0), c.stride(0), s.stride(0), 0, _stream())
+                     x2.stride(0), c.stride(0), s.stride(0), 0, _stream(), xb)
     return out
 
 
 def mx_gemm_a8_why_not(xq, mw, epi: int = 0,
                        residual: Optional[torch.Tensor] = None) -> str:
-    """'' when mx_gemm_a8 takes this call (xq an "mxfp8" MXWeight [M, K]),
-    else why not."""
+    """'' when mx_gemm_a8 takes this call (xq an "mxfp8" MXWeight [M, K],
+    or an "mxfp4" one against an "mxfp4" weight), else why not."""
     from tepdist_amd.ops import mx
     if residual is not None and (residual.dtype != BF16 or residual.dim() != 2
                                  or residual.stride(1) != 1):
         return "residual must be 2-D bf16 with a contiguous last dim"
-    if xq.fmt != "mxfp8":
-        return "activations must be mxfp8"
+    if xq.fmt not in mx.FORMATS:
+        return "activations must be mxfp8 or mxfp4"
     M, K = xq.shape
     N = mw.shape[0]
     if mw.shape[1] != K:
@@ -502,7 +504,7 @@ def mx_gemm_a8_why_not(xq, mw, epi: int = 0,
                    "contiguous last dim"
     why = ext.mx_gemm_a8_plan(M, N, K, mx.bits(mw.fmt), mw.codes.stride(0),
                               mw.scales.stride(0), xq.codes.stride(0),
-                              xq.scales.stride(0), epi)[3]
+                              xq.scales.stride(0), epi, 0, mx.bits(xq.fmt))[3]
     if why:
         return why
     for w in (xq, mw):
@@ -535,11 +537,12 @@ def _mx_gemm_a8_raw(xq, mw, bias, residual, epi, tile: int = 0, out=None):
                    xq.codes.stride(0), xq.scales.stride(0),
                    mw.codes.stride(0), mw.scales.stride(0),
                    residual.stride(0) if residual is not None else 0,
-                   y.stride(0), epi, tile, _stream())
+                   y.stride(0), epi, tile, _stream(), mx.bits(xq.fmt))
     return y
 
 
-def linear_mx_a8(x, mw, bias=None, act: str = "none", residual=None):
+def linear_mx_a8(x, mw, bias=None, act: str = "none", residual=None,
+                 act_format: str = "mxfp8"):
     from tepdist_amd.ops import mx
     N = mw.shape[0]
     if isinstance(x, mx.MXWeight):
@@ -548,7 +551,11 @@ def linear_mx_a8(x, mw, bias=None, act: str = "none", residual=None):
         if x.shape[-1] % 128:   # before the quantizer's weaker K % 32
             raise ValueError("linear_mx_a8: not covered by the scaled-MFMA "
                              "kernel: K must be a positive multiple of 128")
-        xq, lead = mx_quantize_act(x), x.shape[:-1]
+        if mx.bits(act_format) == 4 and mx.bits(mw.fmt) != 4:  # no launch
+            raise ValueError("linear_mx_a8: not covered by the scaled-MFMA "
+                             "kernel: mxfp4 activations need mxfp4 weights "
+                             "(W8A4 is not built)")
+        xq, lead = mx_quantize_act(x, fmt=act_format), x.shape[:-1]
     r2 = None if residual is None else residual.reshape(-1, N)
     y = _mx_gemm_a8_raw(xq, mw, bias, r2, skinny_epi(bias, act, residual))
     return y.reshape(*lead, N)

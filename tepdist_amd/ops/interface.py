@@ -397,26 +397,33 @@ def linear_mx(x, mw, bias=None, act: str = "none", residual=None):
     return _backend(x).linear_mx(x, mw, bias, act, residual)
 
 
-def mx_quantize_act(x, roundtrip: bool = False, out=None):
-    """MXFP8 quantization of activations x [..., K] (bf16, K a multiple of
-    32) by the rule of ops.mx_quantize(x, "mxfp8"), bit for bit: one e8m0
-    scale byte per 32 k, e4m3 elements. roundtrip=False returns an
-    ops.mx.MXWeight of shape (M, K), M the product of the leading dims;
-    roundtrip=True the dequantized values as a tensor like x (exact in bf16).
-    out: the MXWeight or tensor to write into, so a captured step allocates
-    nothing. On the GPU one HIP launch (csrc/mx_act_quant.hip): rows may be
-    strided, 16-byte aligned. Inference only."""
+def mx_quantize_act(x, roundtrip: bool = False, out=None,
+                    fmt: str = "mxfp8"):
+    """MX quantization of activations x [..., K] (bf16, K a multiple of 32)
+    by the rule of ops.mx_quantize(x, fmt), bit for bit: one e8m0 scale byte
+    per 32 k; fmt "mxfp8" (default) = e4m3 elements, codes [M, K]; "mxfp4" =
+    e2m1 elements, codes [M, K / 2] with even k in the low nibble.
+    roundtrip=False returns an ops.mx.MXWeight of shape (M, K), M the product
+    of the leading dims; roundtrip=True the dequantized values as a tensor
+    like x (exact in bf16). out: the MXWeight or tensor to write into, so a
+    captured step allocates nothing. On the GPU one HIP launch (csrc/
+    mx_act_quant.hip): rows may be strided, 16-byte aligned (code rows of
+    out: 8-byte). Inference only."""
     _no_backward("mx_quantize_act", x)
-    return _backend(x).mx_quantize_act(x, roundtrip, out)
+    return _backend(x).mx_quantize_act(x, roundtrip, out, fmt)
 
 
-def linear_mx_a8(x, mw, bias=None, act: str = "none", residual=None):
-    """linear_mx with MXFP8 activations (W4A8 / W8A8): x is a bf16 tensor
-    [..., K], quantized by mx_quantize_act in one launch, or an activation
-    MXWeight [M, K] from it (shared by several linears). The result is
-    defined in fp64 as dq(Xq) . dq(W)^T + bias + residual, then act, rounded
-    once to bf16; it is computed with fp32 accumulation. This is a different
-    model from linear_mx on the same x: the activations are rounded to e4m3
+def linear_mx_a8(x, mw, bias=None, act: str = "none", residual=None,
+                 act_format: str = "mxfp8"):
+    """linear_mx with MX activations, a8 and a4 (W4A8 / W8A8, and W4A4): x is
+    a bf16 tensor [..., K], quantized to act_format ("mxfp8" | "mxfp4") by
+    mx_quantize_act in one launch, or an activation MXWeight [M, K] from it
+    (shared by several linears), whose own fmt then decides. mxfp4
+    activations need an mxfp4 weight: against an mxfp8 one the call raises
+    ValueError (W8A4 is not built). The result is defined in fp64 as dq(Xq)
+    . dq(W)^T + bias + residual, then act, rounded once to bf16; it is
+    computed with fp32 accumulation. This is a different model from
+    linear_mx on the same x: the activations are rounded to e4m3 or e2m1
     blocks. On the GPU this is the scaled-MFMA kernel (csrc/mx_gemm_a8.hip),
     which multiplies codes by codes and never dequantizes either operand: K
     a multiple of 128, code rows 16-byte and scale rows 4-byte aligned on
@@ -425,7 +432,7 @@ def linear_mx_a8(x, mw, bias=None, act: str = "none", residual=None):
     from tepdist_amd.ops.mx import MXWeight
     t = x.codes if isinstance(x, MXWeight) else x
     _no_backward("linear_mx_a8", t, bias, residual)
-    return _backend(t).linear_mx_a8(x, mw, bias, act, residual)
+    return _backend(t).linear_mx_a8(x, mw, bias, act, residual, act_format)
 
 
 def swiglu_linear_decode_mx(x, mw_gate, mw_up):

@@ -113,11 +113,12 @@ def linear_mx(x: torch.Tensor, mw, bias=None, act: str = "none",
     return linear_decode(x, mx_dequantize(mw), bias, act, residual)
 
 
-def mx_quantize_act(x: torch.Tensor, roundtrip: bool = False, out=None):
-    """mx.mx_quantize(x, "mxfp8") on x [..., K] flattened to [M, K]; with
+def mx_quantize_act(x: torch.Tensor, roundtrip: bool = False, out=None,
+                    fmt: str = "mxfp8"):
+    """mx.mx_quantize(x, fmt) on x [..., K] flattened to [M, K]; with
     roundtrip its mx.dequantize_ref in x's shape and dtype."""
     from tepdist_amd.ops import mx
-    q = mx.mx_quantize(x.reshape(-1, x.shape[-1]), "mxfp8")
+    q = mx.mx_quantize(x.reshape(-1, x.shape[-1]), fmt)
     if roundtrip:
         d = mx.dequantize_ref(q).to(x.dtype).reshape(x.shape)
         return d if out is None else out.copy_(d)
@@ -128,12 +129,18 @@ def mx_quantize_act(x: torch.Tensor, roundtrip: bool = False, out=None):
     return q
 
 
-def linear_mx_a8(x, mw, bias=None, act: str = "none", residual=None):
-    """linear_mx on the MXFP8 round trip of x (a tensor, or an activation
-    MXWeight [M, K], whose result is bf16)."""
+def linear_mx_a8(x, mw, bias=None, act: str = "none", residual=None,
+                 act_format: str = "mxfp8"):
+    """linear_mx on the act_format round trip of x (a tensor, or an
+    activation MXWeight [M, K] of either format, whose result is bf16).
+    mxfp4 activations against an mxfp8 weight raise, as on the GPU."""
     from tepdist_amd.ops import mx
+    xfmt = x.fmt if isinstance(x, mx.MXWeight) else act_format
+    if mx.bits(xfmt) == 4 and mx.bits(mw.fmt) != 4:
+        raise ValueError("linear_mx_a8: mxfp4 activations need mxfp4 weights "
+                         "(W8A4 is not built)")
     xd = mx.dequantize_ref(x) if isinstance(x, mx.MXWeight) else \
-        mx_quantize_act(x, roundtrip=True)
+        mx_quantize_act(x, roundtrip=True, fmt=act_format)
     return linear_mx(xd, mw, bias, act, residual)
 
 
