@@ -42,7 +42,22 @@ profiles/linear_mx_a4.json. Contenders, all in the same windows:
   "library"  the W4A4 model on the library: the mxfp4 round trip +
              ops.mx_dequantize + ops.linear and the engine's tail launches.
 `wins`: the slowest "quant_a4" window beats the fastest "library" window;
-`beats_a8`: it beats the fastest "quant_a8" window."""
+`beats_a8`: it beats the fastest "quant_a8" window.
+
+--mlp: Llama's whole MLP under MX activations (llama-1b-gqa: I 6144, d 2048),
+M as above, the three (weight, activation) format pairs, to
+profiles/mlp_mx_a8.json. Contenders, all in the same windows:
+  "composed" ops.mx_quantize_act + two ops.linear_mx_a8 + ops.swiglu + the
+             down call with its own quantizer and the residual, as the engine
+             runs it under mx_mlp="composed";
+  "fused"    ops.mx_quantize_act + ops.linear_mx_a8(act="swiglu", up=,
+             out_format=) (csrc/mx_swiglu_a8.hip) writing MX + the down GEMM
+             on those codes: mx_mlp="fused";
+  "gate_up_composed", "gate_up_fused"  the part between the first quantizer
+             and the down GEMM alone, on x quantized beforehand: two GEMMs +
+             ops.swiglu + the quantizer of h, against the one fused launch.
+`wins`: the slowest "fused" window beats the fastest "composed" window;
+`gate_up_wins`: the same for the gate/up part."""
 import json
 import os
 import statistics
@@ -293,6 +308,77 @@ def run_site_a4(model, site, N, K, form, ms):
     return rows
 
 
+def run_mlp(ms, model="llama-1b-gqa", I=6144, d=2048):
+    torch.manual_seed(0)
+    wg, wu = (torch.randn(I, d, dtype=BF16, device="cuda") * d ** -0.5
+              for _ in range(2))
+    wd = torch.randn(d, I, dtype=BF16, device="cuda") * I ** -0.5
+    rows = []
+    for wfmt, xfmt in (("mxfp4", "mxfp8"), ("mxfp8", "mxfp8"),
+                       ("mxfp4", "mxfp4")):
+        q = [ops.mx_quantize(t, wfmt) for t in (wg, wu, wd)]
+        nbytes = sum(m.nbytes for m in q)
+        sets = max(4, -(-COLD_BYTES // nbytes))
+        g, u, dn = ([mx.MXWeight(m.codes.clone(), m.scales.clone(), m.fmt,
+                                 m.shape) for _ in range(sets)] for m in q)
+        for M in ms:
+            x = torch.randn(M, d, dtype=BF16, device="cuda")
+            xq = ops.mx_quantize_act(x, fmt=xfmt)
+
+            def gate_up(xin, i):
+                return ops.swiglu(ops.linear_mx_a8(xin, g[i]),
+                                  ops.linear_mx_a8(xin, u[i]))
+
+            def fused_gate_up(xin, i):
+                return ops.linear_mx_a8(xin, g[i], act="swiglu", up=u[i],
+                                        out_format=xfmt)
+
+            def quant():
+                return ops.mx_quantize_act(x, out=xq, fmt=xfmt)
+
+            fns = {
+                "composed": lambda i: ops.linear_mx_a8(
+                    gate_up(quant(), i), dn[i], residual=x, act_format=xfmt),
+                "fused": lambda i: ops.linear_mx_a8(
+                    fused_gate_up(quant(), i), dn[i], residual=x),
+                "gate_up_composed": lambda i: ops.mx_quantize_act(
+                    gate_up(xq, i), fmt=xfmt).codes,
+                "gate_up_fused": lambda i: fused_gate_up(xq, i).codes,
+            }
+            graphs, outs = {}, {}
+            for name, fn in fns.items():
+                graphs[name], outs[name] = capture(fn, sets)
+            t = {k: [] for k in graphs}
+            for _ in range(WINDOWS):
+                for k, gr in graphs.items():
+                    t[k].append(window_us(gr, sets))
+            wb, ldc, lds = mx.bits(wfmt), q[0].codes.stride(0), d // 32
+            tile = hip.ext.mx_swiglu_a8_plan(
+                M, I, d, wb, ldc, lds, I, d, wb, ldc, lds, xq.codes.stride(0),
+                d // 32, 0, 0, mx.bits(xfmt), mx.bits(xfmt),
+                I * mx.bits(xfmt) // 8, I // 32)[0]
+            row = {"bench": "mlp_mx_a8", "model": model, "fmt": wfmt,
+                   "act": xfmt, "M": M, "I": I, "d": d, "tile": tile,
+                   "sets": sets, "weight_bytes": nbytes}
+            for k, v in t.items():
+                row[f"{k}_us"] = round(statistics.median(v), 2)
+                row[f"{k}_us_min_max"] = [round(min(v), 2), round(max(v), 2)]
+            row["wins"] = max(t["fused"]) < min(t["composed"])
+            row["gate_up_wins"] = \
+                max(t["gate_up_fused"]) < min(t["gate_up_composed"])
+            row["gate_up_fused_tflops"] = round(
+                4.0 * M * I * d / (row["gate_up_fused_us"] * 1e-6) / 1e12, 1)
+            row["max_abs_diff_vs_composed"] = round(
+                (outs["fused"].float() - outs["composed"].float())
+                .abs().max().item(), 4)
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+            del graphs, outs
+        del g, u, dn
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main(*argv):
     def opt(name, default):
         return argv[argv.index(name) + 1].split(",") if name in argv \
@@ -305,11 +391,11 @@ def main(*argv):
         raise SystemExit(f"--act must be bf16, mxfp8 or mxfp4, got {act!r}")
     run = {"bf16": run_site, "mxfp8": run_site_a8, "mxfp4": run_site_a4}[act]
     skip = {a for n in ("--sites", "--ms", "--act") if n in argv
-            for a in (n, argv[argv.index(n) + 1])}
+            for a in (n, argv[argv.index(n) + 1])} | {"--mlp"}
     out = next((a for a in argv if a not in skip), None)
-    rows = []
+    rows = run_mlp(ms) if "--mlp" in argv else []
     for s in SITES:
-        if sites is None or s[1] in sites:
+        if "--mlp" not in argv and (sites is None or s[1] in sites):
             rows += run(*s, ms)
     if out:
         with open(out, "w") as f:

@@ -95,6 +95,17 @@ e2m1 x e2m1 form of the scaled MFMA), valid only with weight_format="mxfp4"
 is no "auto" rule yet (docs/KERNELS.md "MX weights x MXFP8 activations", "MX
 weights x MXFP4 activations").
 
+Llama's MLP under an MX act_format (mx_mlp=, or TEPDIST_MX_MLP): "composed"
+(default) = the path above, unchanged. "fused" = at the sites of T > 1 or
+M > 64 the MLP is three launches: ops.mx_quantize_act of the normed input,
+ops.linear_mx_a8(..., act="swiglu", up=, out_format=act_format), which
+computes gate, up and silu(g) * u in one kernel and writes the hidden
+activations as MX codes, and ops.linear_mx_a8 of those codes against w_down
+with the residual. It rounds silu(g) * u once where the composed path rounds
+g and u to bf16 first: yet another model, on CPU (the reference ops) and GPU
+alike. It needs an act_format other than "bf16"; single-token sites and GPT-2
+are unchanged (docs/KERNELS.md "Fused SwiGLU gate/up on MX activations").
+
 KV cache format (kv_format=, or TEPDIST_KV_FORMAT): "bf16" (default) = every
 path above as it was. "mxfp8" = the caches are mx.MXCache (e4m3 codes and one
 e8m0 scale byte per 32 elements of a row, 51.6 % of the bf16 bytes): every
@@ -133,7 +144,8 @@ class Generator:
                  weight_format: Optional[str] = None,
                  mx_linear: Optional[str] = None,
                  act_format: Optional[str] = None,
-                 kv_format: Optional[str] = None):
+                 kv_format: Optional[str] = None,
+                 mx_mlp: Optional[str] = None):
         assert model.env.tp_size == 1, "generation engine: tp=1 layout"
         self.m = model
         self.cfg = model.cfg
@@ -201,6 +213,16 @@ class Generator:
             raise ValueError(
                 f"kv_format must be 'bf16' or 'mxfp8', got {kv_format!r}")
         self.kv_format = kv_format
+        if mx_mlp is None:
+            mx_mlp = os.environ.get("TEPDIST_MX_MLP", "composed")
+        if mx_mlp not in ("composed", "fused"):
+            raise ValueError(
+                f"mx_mlp must be 'composed' or 'fused', got {mx_mlp!r}")
+        if mx_mlp == "fused" and act_format == "bf16":
+            raise ValueError(
+                "mx_mlp='fused' needs an MX act_format, got act_format="
+                f"{act_format!r}")
+        self.mx_mlp = mx_mlp
         # id(parameter) -> its MXWeight; empty = serve the bf16 weights
         self.mxw = {}
         if weight_format != "bf16":
@@ -489,6 +511,13 @@ class Generator:
         if mg is not None and self.act_format != "bf16":
             if T == 1 and self._mx_site(hn, mg, mw_up=mu):
                 h = ops.swiglu_linear_decode_mx(self._roundtrip(hn), mg, mu)
+            elif self.mx_mlp == "fused":    # quantizer, gate/up/swiglu, down
+                xq = ops.mx_quantize_act(hn, fmt=self.act_format)
+                hq = ops.linear_mx_a8(xq, mg, act="swiglu", up=mu,
+                                      out_format=self.act_format)
+                y = ops.linear_mx_a8(hq, self.mxw[id(blk.w_down)],
+                                     residual=x.reshape(B * T, d))
+                return y.reshape(x.shape)
             else:               # one quantization, shared by gate and up
                 xq = ops.mx_quantize_act(hn, fmt=self.act_format)
                 h = ops.swiglu(ops.linear_mx_a8(xq, mg),

@@ -33,6 +33,7 @@ SOURCES = [
     "skinny_mx_gemm.hip",
     "mx_gemm.hip",
     "mx_gemm_a8.hip",
+    "mx_swiglu_a8.hip",
     "mx_act_quant.hip",
     "sampling.hip",
     "moe_route.hip",
@@ -94,6 +95,7 @@ def _needs_build() -> bool:
                                           CSRC / "skinny_mx_plan.h",
                                           CSRC / "mx_gemm_plan.h",
                                           CSRC / "mx_gemm_a8_plan.h",
+                                          CSRC / "mx_swiglu_a8_plan.h",
                                           CSRC / "mx_dequant.h",
                                           CSRC / "mx_kv.h",
                                           CSRC / "gemm_tile.h",

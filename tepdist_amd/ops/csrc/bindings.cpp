@@ -17,6 +17,7 @@
 #include "gemm_plan.h"
 #include "kernels.h"
 #include "mx_gemm_a8_plan.h"
+#include "mx_swiglu_a8_plan.h"
 #include "mx_gemm_plan.h"
 #include "skinny_mx_plan.h"
 #include "skinny_plan.h"
@@ -248,6 +249,52 @@ PYBIND11_MODULE(_tepdist_hip, m) {
      py::arg("ld_wcodes"), py::arg("ld_wscales"), py::arg("ld_xcodes"),
      py::arg("ld_xscales"), py::arg("epi") = 0, py::arg("tile") = 0,
      py::arg("x_bits") = 8);
+
+  // out_bits 0: y is written; 8 | 4: ocodes and oscales are
+  m.def("mx_swiglu_a8", [](uintptr_t xcodes, uintptr_t xscales,
+                           uintptr_t gcodes, uintptr_t gscales,
+                           uintptr_t ucodes, uintptr_t uscales, uintptr_t y,
+                           uintptr_t ocodes, uintptr_t oscales, int M, int I,
+                           int K, int bits, int64_t ldxc, int64_t ldxs,
+                           int64_t ldc, int64_t lds, int64_t ldy, int64_t ldoc,
+                           int64_t ldos, int tile, uintptr_t stream,
+                           int x_bits, int out_bits) {
+    auto p = [](uintptr_t v) { return reinterpret_cast<void*>(v); };
+    mx_swiglu_a8(p(xcodes), p(xscales), p(gcodes), p(gscales), p(ucodes),
+                 p(uscales), p(y), p(ocodes), p(oscales), M, I, K, bits, ldxc,
+                 ldxs, ldc, lds, ldy, ldoc, ldos, tile, S(stream), x_bits,
+                 out_bits);
+    check_launch();
+  }, py::arg("xcodes"), py::arg("xscales"), py::arg("gcodes"),
+     py::arg("gscales"), py::arg("ucodes"), py::arg("uscales"), py::arg("y"),
+     py::arg("ocodes"), py::arg("oscales"), py::arg("M"), py::arg("I"),
+     py::arg("K"), py::arg("bits"), py::arg("ldxc"), py::arg("ldxs"),
+     py::arg("ldc"), py::arg("lds"), py::arg("ldy"), py::arg("ldoc"),
+     py::arg("ldos"), py::arg("tile"), py::arg("stream"), py::arg("x_bits"),
+     py::arg("out_bits"));
+
+  // (tile, stages, blocks, why_not) — host-only, no GPU. tile = the token
+  // rows of a block (128 x 64 hidden, or 64 x 32)
+  m.def("mx_swiglu_a8_plan", [](int M, int I, int K, int bits,
+                                int64_t ld_wcodes, int64_t ld_wscales,
+                                int up_I, int up_K, int up_bits,
+                                int64_t ld_ucodes, int64_t ld_uscales,
+                                int64_t ld_xcodes, int64_t ld_xscales, int epi,
+                                int tile, int x_bits, int out_bits,
+                                int64_t ld_ocodes, int64_t ld_oscales) {
+    const MxGemmPlan p = mx_swiglu_a8_plan(
+        M, I, K, bits, ld_wcodes, ld_wscales, up_I, up_K, up_bits, ld_ucodes,
+        ld_uscales, ld_xcodes, ld_xscales, epi, tile, x_bits, out_bits,
+        ld_ocodes, ld_oscales);
+    return py::make_tuple(p.tile, p.stages, p.blocks,
+                          p.why_not ? p.why_not : "");
+  }, py::arg("M"), py::arg("I"), py::arg("K"), py::arg("bits"),
+     py::arg("ld_wcodes"), py::arg("ld_wscales"), py::arg("up_I"),
+     py::arg("up_K"), py::arg("up_bits"), py::arg("ld_ucodes"),
+     py::arg("ld_uscales"), py::arg("ld_xcodes"), py::arg("ld_xscales"),
+     py::arg("epi") = 0, py::arg("tile") = 0, py::arg("x_bits") = 8,
+     py::arg("out_bits") = 0, py::arg("ld_ocodes") = 0,
+     py::arg("ld_oscales") = 0);
 
   m.def("transpose", [](uintptr_t in, uintptr_t out, int R, int C,
                         int64_t si, int64_t so, int batch,

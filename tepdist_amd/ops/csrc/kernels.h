@@ -115,6 +115,20 @@ void mx_gemm_a8(const void* xcodes, const void* xscales, const void* codes,
                 int64_t ldxs, int64_t ldc, int64_t lds, int64_t ldr,
                 int64_t ldy, int epi, int tile, hipStream_t stream,
                 int x_bits = 8);
+// h[M, I] = bf16(silu(G) * U), G / U = dq(Xq)[M, K] @ dq(Wg / Wu)[I, K]^T on
+// the scaled MFMA (mx_swiglu_a8.hip): one launch for gate, up and swiglu, one
+// rounding. Gate and up share bits and the row strides ldc / lds. out_bits 0:
+// y [M, I] bf16 (ldy elements), ocodes / oscales null. out_bits 8 | 4: h
+// quantized by the rule of mx_quantize(h, "mxfp8" | "mxfp4") into ocodes
+// (ldoc bytes) and oscales [M, I / 32] (ldos), y null; needs I % 32 == 0. No
+// workspace, no atomics. Throws with mx_swiglu_a8_plan()'s reason when the
+// call is not covered.
+void mx_swiglu_a8(const void* xcodes, const void* xscales, const void* gcodes,
+                  const void* gscales, const void* ucodes, const void* uscales,
+                  void* y, void* ocodes, void* oscales, int M, int I, int K,
+                  int bits, int64_t ldxc, int64_t ldxs, int64_t ldc,
+                  int64_t lds, int64_t ldy, int64_t ldoc, int64_t ldos,
+                  int tile, hipStream_t stream, int x_bits, int out_bits);
 
 // --- Transpose -------------------------------------------------------------
 // out[c][r] = in[r][c] per batch (strides in elements).

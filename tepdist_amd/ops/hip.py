@@ -541,10 +541,109 @@ def _mx_gemm_a8_raw(xq, mw, bias, residual, epi, tile: int = 0, out=None):
     return y
 
 
+# The fused SwiGLU gate/up form of the same GEMM (csrc/mx_swiglu_a8.hip):
+# both products from one staging of xq, silu(g) * u on the accumulators, h
+# written as bf16 or as an activation MXWeight. Coverage and tile come from
+# csrc/mx_swiglu_a8_plan.h (ext.mx_swiglu_a8_plan).
+
+def mx_swiglu_a8_why_not(xq, mw, mw_up, out_format: Optional[str] = None,
+                         out=None) -> str:
+    """'' when mx_swiglu_a8 takes this call (xq an activation MXWeight
+    [M, K], mw / mw_up the gate and up MXWeights [I, K], out_format None,
+    "mxfp8" or "mxfp4", out the tensor or MXWeight to write), else why not."""
+    from tepdist_amd.ops import mx
+    if xq.fmt not in mx.FORMATS:
+        return "activations must be mxfp8 or mxfp4"
+    if out_format is not None and out_format not in mx.FORMATS:
+        return "out_format must be None, 'mxfp8' or 'mxfp4'"
+    M, K = xq.shape
+    I = mw.shape[0]
+    if mw.shape[1] != K:
+        return "weight shape does not match x"
+    for w in (xq, mw, mw_up):
+        mx.check(w)
+        if w.codes.stride(1) != 1 or w.scales.stride(1) != 1 or \
+                not w.codes.is_cuda or not w.scales.is_cuda:
+            return "codes and scales must be device tensors with a " \
+                   "contiguous last dim"
+    ob = mx.bits(out_format) if out_format else 0
+    ldoc, ldos = (I * ob // 8, I // 32) if out is None or not ob else \
+        (out.codes.stride(0), out.scales.stride(0))
+    why = ext.mx_swiglu_a8_plan(
+        M, I, K, mx.bits(mw.fmt), mw.codes.stride(0), mw.scales.stride(0),
+        mw_up.shape[0], mw_up.shape[1], mx.bits(mw_up.fmt),
+        mw_up.codes.stride(0), mw_up.scales.stride(0), xq.codes.stride(0),
+        xq.scales.stride(0), 0, 0, mx.bits(xq.fmt), ob, ldoc, ldos)[3]
+    if why:
+        return why
+    for w in (xq, mw, mw_up):
+        if w.codes.data_ptr() % 16 or w.scales.data_ptr() % 4:
+            return "codes need a 16-byte-aligned base, scales a " \
+                   "4-byte-aligned one"
+    return ""
+
+
+def _mx_swiglu_a8_raw(xq, mw, mw_up, out_format: Optional[str] = None,
+                      tile: int = 0, out=None):
+    """One mx_swiglu_a8 launch on quantized activations xq [M, K]. tile: 0 =
+    the plan's choice, else 64 or 128 (token rows of a block). out: what to
+    write, a bf16 [M, I] view with a contiguous last dim (out_format None)
+    or an out_format MXWeight [M, I] of uint8 views with 8-byte-aligned code
+    rows."""
+    from tepdist_amd.ops import mx
+    why = mx_swiglu_a8_why_not(xq, mw, mw_up, out_format, out)
+    if why:
+        raise ValueError(f"linear_mx_a8: not covered by the fused swiglu "
+                         f"kernel: {why}")
+    M, K = xq.shape
+    I = mw.shape[0]
+    dev = xq.codes.device
+    ob = mx.bits(out_format) if out_format else 0
+    y = c = s = None
+    if not ob:
+        y = torch.empty(M, I, dtype=BF16, device=dev) if out is None else out
+        assert y.dtype == BF16 and tuple(y.shape) == (M, I) \
+            and y.stride(1) == 1
+    else:
+        if out is None:
+            out = mx.MXWeight(
+                torch.empty(M, I * ob // 8, dtype=torch.uint8, device=dev),
+                torch.empty(M, I // 32, dtype=torch.uint8, device=dev),
+                out_format, (M, I))
+        c, s = out.codes, out.scales
+        if out.fmt != out_format or tuple(out.shape) != (M, I) or \
+                mx.check(out) != (M, I) or c.stride(1) != 1 or \
+                s.stride(1) != 1 or not c.is_cuda or not s.is_cuda or \
+                c.data_ptr() % 8:
+            raise ValueError(
+                f"linear_mx_a8: out must be an {out_format} MXWeight of "
+                f"shape {(M, I)} on the device with an 8-byte-aligned code "
+                "base")
+    ext.mx_swiglu_a8(xq.codes.data_ptr(), xq.scales.data_ptr(),
+                     mw.codes.data_ptr(), mw.scales.data_ptr(),
+                     mw_up.codes.data_ptr(), mw_up.scales.data_ptr(), _p(y),
+                     _p(c), _p(s), M, I, K, mx.bits(mw.fmt),
+                     xq.codes.stride(0), xq.scales.stride(0),
+                     mw.codes.stride(0), mw.scales.stride(0),
+                     y.stride(0) if y is not None else 0,
+                     c.stride(0) if ob else 0, s.stride(0) if ob else 0,
+                     tile, _stream(), mx.bits(xq.fmt), ob)
+    return out if ob else y
+
+
 def linear_mx_a8(x, mw, bias=None, act: str = "none", residual=None,
-                 act_format: str = "mxfp8"):
+                 act_format: str = "mxfp8", up=None, out_format=None):
     from tepdist_amd.ops import mx
     N = mw.shape[0]
+    swiglu = act == "swiglu"
+    if swiglu and (bias is not None or residual is not None):
+        raise ValueError("linear_mx_a8: act='swiglu' takes no bias and no "
+                         "residual")
+    if swiglu != (up is not None):
+        raise ValueError("linear_mx_a8: act='swiglu' and up= (the up "
+                         "projection's MXWeight) go together")
+    if out_format is not None and not swiglu:
+        raise ValueError("linear_mx_a8: out_format needs act='swiglu'")
     if isinstance(x, mx.MXWeight):
         xq, lead = x, x.shape[:1]
     else:
@@ -556,6 +655,9 @@ def linear_mx_a8(x, mw, bias=None, act: str = "none", residual=None,
                              "kernel: mxfp4 activations need mxfp4 weights "
                              "(W8A4 is not built)")
         xq, lead = mx_quantize_act(x, fmt=act_format), x.shape[:-1]
+    if swiglu:
+        h = _mx_swiglu_a8_raw(xq, mw, up, out_format)
+        return h if out_format else h.reshape(*lead, N)
     r2 = None if residual is None else residual.reshape(-1, N)
     y = _mx_gemm_a8_raw(xq, mw, bias, r2, skinny_epi(bias, act, residual))
     return y.reshape(*lead, N)

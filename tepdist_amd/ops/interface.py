@@ -414,7 +414,7 @@ def mx_quantize_act(x, roundtrip: bool = False, out=None,
 
 
 def linear_mx_a8(x, mw, bias=None, act: str = "none", residual=None,
-                 act_format: str = "mxfp8"):
+                 act_format: str = "mxfp8", up=None, out_format=None):
     """linear_mx with MX activations, a8 and a4 (W4A8 / W8A8, and W4A4): x is
     a bf16 tensor [..., K], quantized to act_format ("mxfp8" | "mxfp4") by
     mx_quantize_act in one launch, or an activation MXWeight [M, K] from it
@@ -428,11 +428,25 @@ def linear_mx_a8(x, mw, bias=None, act: str = "none", residual=None,
     which multiplies codes by codes and never dequantizes either operand: K
     a multiple of 128, code rows 16-byte and scale rows 4-byte aligned on
     both sides; a call it does not cover raises ValueError with the reason.
-    Inference only."""
+
+    act="swiglu" is the fused gate/up site of a SwiGLU MLP: mw is the gate
+    weight, up= the up weight (an MXWeight of mw's format, shape and
+    strides), and neither bias nor residual is taken (ValueError). The
+    result is h = bf16(silu(G) * U), G and U defined in fp64 as dq(Xq) .
+    dq(mw)^T and dq(Xq) . dq(up)^T, rounded once; computed with fp32
+    accumulation and silu(g) * u on the fp32 sums. This is a different model
+    from ops.swiglu on two linear_mx_a8 results, which rounds g and u to bf16
+    first. out_format (only with act="swiglu"): None returns h as bf16
+    [..., I]; "mxfp8" or "mxfp4" returns mx.mx_quantize(h, out_format), bit
+    for bit, as an activation MXWeight [M, I] that a following linear_mx_a8
+    takes as its x (I a multiple of 32). On the GPU one launch of csrc/
+    mx_swiglu_a8.hip; g, u and, with out_format, the bf16 h never reach
+    memory. Inference only."""
     from tepdist_amd.ops.mx import MXWeight
     t = x.codes if isinstance(x, MXWeight) else x
     _no_backward("linear_mx_a8", t, bias, residual)
-    return _backend(t).linear_mx_a8(x, mw, bias, act, residual, act_format)
+    return _backend(t).linear_mx_a8(x, mw, bias, act, residual, act_format,
+                                    up, out_format)
 
 
 def swiglu_linear_decode_mx(x, mw_gate, mw_up):

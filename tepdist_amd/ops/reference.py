@@ -130,18 +130,43 @@ def mx_quantize_act(x: torch.Tensor, roundtrip: bool = False, out=None,
 
 
 def linear_mx_a8(x, mw, bias=None, act: str = "none", residual=None,
-                 act_format: str = "mxfp8"):
+                 act_format: str = "mxfp8", up=None, out_format=None):
     """linear_mx on the act_format round trip of x (a tensor, or an
     activation MXWeight [M, K] of either format, whose result is bf16).
-    mxfp4 activations against an mxfp8 weight raise, as on the GPU."""
+    mxfp4 activations against an mxfp8 weight raise, as on the GPU.
+    act="swiglu" with up=: h = bf16(silu(G) * U) with G and U the fp64
+    products of the dequantized operands, then mx.mx_quantize(h, out_format)
+    if out_format is set."""
     from tepdist_amd.ops import mx
     xfmt = x.fmt if isinstance(x, mx.MXWeight) else act_format
     if mx.bits(xfmt) == 4 and mx.bits(mw.fmt) != 4:
         raise ValueError("linear_mx_a8: mxfp4 activations need mxfp4 weights "
                          "(W8A4 is not built)")
+    swiglu = act == "swiglu"
+    if swiglu and (bias is not None or residual is not None):
+        raise ValueError("linear_mx_a8: act='swiglu' takes no bias and no "
+                         "residual")
+    if swiglu != (up is not None):
+        raise ValueError("linear_mx_a8: act='swiglu' and up= go together")
+    if out_format is not None and not swiglu:
+        raise ValueError("linear_mx_a8: out_format needs act='swiglu'")
     xd = mx.dequantize_ref(x) if isinstance(x, mx.MXWeight) else \
         mx_quantize_act(x, roundtrip=True, fmt=act_format)
-    return linear_mx(xd, mw, bias, act, residual)
+    if not swiglu:
+        return linear_mx(xd, mw, bias, act, residual)
+    if up.fmt != mw.fmt or tuple(up.shape) != tuple(mw.shape):
+        raise ValueError("linear_mx_a8: gate and up must have one format and "
+                         "one shape")
+    if out_format is not None and mw.shape[0] % 32:
+        raise ValueError("linear_mx_a8: a quantized output needs I to be a "
+                         "multiple of 32")
+    x64 = xd.double()
+    g = x64 @ mx.dequantize_ref(mw).double().t()
+    h = (g * torch.sigmoid(g)
+         * (x64 @ mx.dequantize_ref(up).double().t())).to(torch.bfloat16)
+    if out_format is None:
+        return h
+    return mx.mx_quantize(h.reshape(-1, h.shape[-1]), out_format)
 
 
 def swiglu_linear_decode_mx(x: torch.Tensor, mw_gate, mw_up) -> torch.Tensor:
